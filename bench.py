@@ -203,6 +203,26 @@ def side_workloads():
     return res
 
 
+DUMP_PARAM_SAMPLE = 1 << 22       # 16 MB of fp32: the full parameter set of cfg2 is 0.9 GB
+
+
+def dump_outputs(d, model, agent, last, rank):
+    """--dump-outputs: the losses of the last timed step (loss_<name>.npy) and the fp32 parameters it left behind (param_sample.npy: the
+    sorted, de-duplicated positions a generator seeded with 0 draws over model.named_parameters() laid end to end, so the same model
+    samples the same positions whatever the arena layout).  Called on every rank: under ZeRO-1 gathering the masters is a collective."""
+    if agent.dp is not None:
+        agent.dp.gather_master()
+    if rank != 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    for k, v in last.items():
+        np.save(os.path.join(d, f"loss_{k}.npy"), np.asarray(float(v), dtype=np.float32))
+    flat = torch.cat([p.detach().reshape(-1) for _, p in model.named_parameters()])
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_PARAM_SAMPLE))
+    np.save(os.path.join(d, "param_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+    del flat
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -230,8 +250,13 @@ def main():
                     help="side measurement 'tsv': every step pulls its batch through the input pipeline (TSV rows of base64 JPEG frames "
                          "-> host Huffman decode -> GPU IDCT / resize / crop / normalise, prefetched) and masks it on the host, inside "
                          "the timed region; the contract value keeps inputs resident in HBM")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32): the losses "
+                         "and a fixed, seeded sample of the updated fp32 parameters -- for comparing two builds on the same inputs")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.cpu_baseline_only:
         cpu_baseline_child()
         return
@@ -379,6 +404,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_vals = {k: float(v) for k, v in last.items()}
+    if a.dump_outputs:                                    # before the reference loop and the roofline sampling steps move the parameters on
+        dump_outputs(a.dump_outputs, model, agent, last, rank)
 
     # ---- the reference's own loop semantics (go_dl, main_pretrain_mlm.py:202-232 + step :145-176), timed beside the contract value: per
     # step a HOST batch (pinned, as a DataLoader with pin_memory hands it over), masking() on the host, prepare_batch (H2D of frames,

@@ -218,12 +218,13 @@ def test_checkpoint_contract_round_trip(tmp_path):
 def test_bench_spawns_its_own_ranks_and_refuses_a_wrong_world_size():
     """`python bench.py --gpus N` without a launcher must start N ranks itself (not label a 1-rank run as N GPUs), and a
     launcher world size that contradicts --gpus must fail loudly.  --selftest-launch stops after the rendezvous + all-reduce
-    (gloo on this GPU-less container)."""
+    (gloo: the GPUs are hidden from the ranks, so the check is the same on a host with one GPU or none)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--selftest-launch"], capture_output=True, text=True,
                        timeout=240, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -233,6 +234,28 @@ def test_bench_spawns_its_own_ranks_and_refuses_a_wrong_world_size():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--selftest-launch"], capture_output=True, text=True,
                        timeout=120, env={**env, "WORLD_SIZE": "1", "RANK": "0"})
     assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_writes_the_same_float_arrays_for_the_same_state(tmp_path):
+    """bench.py --dump-outputs: the last step's losses and a seeded sample of the parameters as float .npy files within 64 MB,
+    identical for identical model state (two builds are compared file by file)."""
+    import types
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.Linear(200, 7))
+    flat = torch.cat([p.detach().reshape(-1) for p in m.parameters()]).numpy()
+    got = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), m, types.SimpleNamespace(dp=None), {"mtm": torch.tensor(1.5), "vtm": torch.tensor(0.25)}, 0)
+        got.append({f: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    assert sorted(got[0]) == ["loss_mtm.npy", "loss_vtm.npy", "param_sample.npy"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got[0].values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in got[0]) <= 64 << 20
+    assert got[0]["loss_mtm.npy"] == 1.5 and got[0]["loss_vtm.npy"] == 0.25
+    assert np.isin(got[0]["param_sample.npy"], flat).all() and len(got[0]["param_sample.npy"]) > 0.9 * flat.size
+    assert all(np.array_equal(got[0][f], got[1][f]) for f in got[0])
+    bench.dump_outputs(str(tmp_path / "rank1"), m, types.SimpleNamespace(dp=None), {"mtm": torch.tensor(1.5)}, 1)
+    assert not os.path.exists(tmp_path / "rank1")
 
 
 def test_hf_checkpoint_loader_renames_legacy_layernorm_keys_and_ties_the_decoder(tmp_path):
