@@ -521,6 +521,84 @@ typedef struct lav_swin_block_bwd_desc {
 int lav_swin_block_bwd(void* stream, void* side_stream, const lav_swin_block_bwd_desc* d);
 
 /* ---------------------------------------------------------------------------------------------
+ * Caption decoding with a key / value cache (csrc/decode.hip; LAVENDER_Captioning.generate, model_for_captioning.py:139-500).  Eval only:
+ * no dropout, nothing kept for a backward, no atomics (two runs give the same bits).  Nothing is allocated or synchronised: the caller
+ * owns the cache and every workspace.
+ *
+ * Skinny GEMM: out[M, N] = x[M, K] . W[N, K]^T (+ bias[N]) for 1 <= M <= 64, K a multiple of 32, 16-byte aligned rows.  epi:
+ *   LAV_SKINNY_BF16     bf16 out
+ *   LAV_SKINNY_GELU     bf16 out = gelu(v) (the exact-erf GELU of the fusion GEMM epilogue)
+ *   LAV_SKINNY_RES_F32  fp32 out = v + residual (fp32 rows, or bf16 rows when residual_bf16) -- the post-LN residual adds
+ *   LAV_SKINNY_F32      fp32 out (the MLM decoder logits)
+ * lav_gemm_bf16's tile selection is not affected. */
+#define LAV_SKINNY_BF16 0
+#define LAV_SKINNY_GELU 1
+#define LAV_SKINNY_RES_F32 2
+#define LAV_SKINNY_F32 3
+int lav_gemm_skinny_bf16(void* stream, int M, int N, int K, const void* x, long ldx, const void* w, long ldw, const float* bias, int epi,
+                         const void* residual, long ldr, int residual_bf16, void* out, long ldo);
+
+/* Decode attention, head_dim 64, q_len <= 8 new query rows per (clip, head).  The keys of clip b are, in order:
+ *   [0, Lv)                  video rows read in place from the prefix pass's qkv buffer (row b * Lv + i, stride ld_prefix = 3 hidden),
+ *                            visible where key_mask[b, i] != 0 (key_mask may be NULL: all visible)
+ *   [Lv, Lv + n_cached)      the text cache (B, heads, max_len, 64) bf16, cache_k / cache_v: visible to every new row
+ *   the q_len new rows       their own k / v in qkv_new (row b * q_len + j, stride ld_new): new key j is visible to new rows >= j
+ * out (row b * q_len + j, column head * 64 + d, stride ldo) = softmax(q k^T * scale) v in fp32, stored bf16.  The same launch writes the k / v
+ * of new rows 0 .. n_append - 1 to cache positions n_cached .. n_cached + n_append - 1.  When B * heads is below the CU count the keys are
+ * split over lav_attention_decode_splits(d) workgroups per (clip, head), combined by a second launch in split order: `partials` then needs
+ * B * heads * splits * q_len * 66 floats, and `partials_capacity` states how many it holds (a smaller workspace fails with LAV_E_WORKSPACE
+ * before anything is launched).  The split count never decreases as n_cached grows: a workspace sized for the last step covers every step. */
+typedef struct lav_attn_decode_desc {
+    int B, heads, head_dim, q_len, Lv, n_cached, n_append, max_len;
+    float scale;
+    const void* prefix_qkv; long ld_prefix; const int32_t* key_mask;
+    const void* qkv_new; long ld_new;
+    void* cache_k; void* cache_v;
+    void* out; long ldo;
+    float* partials; long partials_capacity;               /* workspace of the key splits and its size in floats */
+} lav_attn_decode_desc;
+int lav_attention_decode_splits(const lav_attn_decode_desc* d);
+int lav_attention_decode(void* stream, const lav_attn_decode_desc* d);
+
+/* BERT embeddings of n single rows with explicit positions (eval: no dropout): word[ids[r]] + pos[pos_ids[r]] + type0 -> LayerNorm(eps) -> bf16
+ * (n, Hd), Hd <= 1024.  lav_text_embed_fwd hard-wires positions 0 .. X - 1. */
+int lav_text_embed_rows_fwd(void* stream, int n, int Hd, const int64_t* ids, const int32_t* pos_ids, const float* word, const float* pos,
+                            const float* type0, const float* gamma, const float* beta, float eps, void* out);
+
+/* One greedy decoding step over fp32 logits (B, V) with row pitch ld, one workgroup per row (model_for_captioning.py:430-480):
+ *   penalty != 1: every distinct id of ids[b, 0 .. cur) scales its logit IN PLACE (x * penalty if x < 0, else x / penalty);
+ *   tok = argmax (lowest index on a tie), score = log_softmax(logits)[tok];
+ *   u = unfinished[b]: ids[b, cur] = u ? tok : pad_id (also written to next_ids[b * ld_next] when next_ids is not NULL),
+ *   score_sum[b] += u ? score : 0, count[b] += u, unfinished[b] = u && ids[b, cur] != eos_id. */
+int lav_greedy_step(void* stream, int B, int V, float* logits, long ld, int64_t* ids, long ld_ids, int cur, float penalty, int32_t* unfinished,
+                    float* score_sum, float* count, int64_t pad_id, int64_t eos_id, int64_t* next_ids, long ld_next);
+
+/* Stage-level entry of the decode path: one post-LN BertLayer (the arithmetic of lav_bert_layer_fwd, eval) over the q_len new rows of
+ * every clip (rows = B * q_len, row b * q_len + j), with the attention of lav_attention_decode:
+ *   qkv = x Wqkv^T + b;  cx = decode_attention(qkv);  pre1 = res + cx Wao^T + b;  x1 = LN1(pre1);  h = gelu(x1 Wff1^T + b);
+ *   pre2 = x1 + h Wff2^T + b;  y = LN2(pre2)
+ * `res` is x_res (fp32 rows, or bf16 when x_res_bf16: the embeddings in front of the first layer).  pre1, pre2, x1_32 and y32 are fp32
+ * (rows, hidden); y32 is the next layer's residual.  ln_stats: 2 * rows floats of scratch.  rows = B * q_len <= 64 (the skinny GEMM's limit:
+ * LAVENDER_Captioning.generate decodes larger batches in chunks of 32 clips). */
+typedef struct lav_bert_layer_decode_desc {
+    int B, q_len, hidden, heads, ffn, Lv, n_cached, n_append, max_len;
+    float ln_eps, ln2_eps;
+    const int32_t* key_mask;
+    const void* w_qkv; const float* b_qkv;
+    const void* w_ao; const float* b_ao; const float* ln1_gamma; const float* ln1_beta;
+    const void* w_ff1; const float* b_ff1;
+    const void* w_ff2; const float* b_ff2; const float* ln2_gamma; const float* ln2_beta;
+    const void* prefix_qkv;                                /* this layer's qkv of the video rows, (B * Lv, 3 hidden) bf16 */
+    void* cache_k; void* cache_v;                          /* this layer's text cache, (B, heads, max_len, 64) bf16 each */
+    const void* x;                                         /* bf16 (rows, hidden) */
+    const void* x_res; int x_res_bf16;
+    void* qkv; void* cx; float* pre1; void* x1; float* x1_32; void* h; float* pre2; float* ln_stats;
+    void* y; float* y32;                                   /* outputs: bf16 (next GEMM operand) and fp32 (next residual) */
+    float* attn_partials; long attn_partials_capacity;     /* lav_attention_decode's partials and their size in floats (NULL, 0 when it needs none) */
+} lav_bert_layer_decode_desc;
+int lav_bert_layer_decode(void* stream, const lav_bert_layer_decode_desc* d);
+
+/* ---------------------------------------------------------------------------------------------
  * Process-wide probe switches: environment variables read ONCE by the library on first use (not part of the contract; every setting
  * computes the same results up to fp32 summation order unless stated).  They exist so that tools/ and profiles/ can A/B a kernel
  * choice on one box.

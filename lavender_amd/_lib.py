@@ -96,6 +96,21 @@ class SwinBlockBwdDesc(C.Structure):       # struct lav_swin_block_bwd_desc
                 [(n, vp) for n in ("dh", "d_y2", "d_mid", "d_ao", "dqkv", "d_y1", "dx")] + [("group_splits", i32), ("assign_mask", i32)])
 
 
+class AttnDecodeDesc(C.Structure):         # struct lav_attn_decode_desc
+    _fields_ = ([(n, i32) for n in ("B", "heads", "head_dim", "q_len", "Lv", "n_cached", "n_append", "max_len")] + [("scale", f32)] +
+                [("prefix_qkv", vp), ("ld_prefix", i64), ("key_mask", vp), ("qkv_new", vp), ("ld_new", i64), ("cache_k", vp), ("cache_v", vp),
+                 ("out", vp), ("ldo", i64), ("partials", vp), ("partials_capacity", i64)])
+
+
+class BertLayerDecodeDesc(C.Structure):    # struct lav_bert_layer_decode_desc
+    _fields_ = ([(n, i32) for n in ("B", "q_len", "hidden", "heads", "ffn", "Lv", "n_cached", "n_append", "max_len")] +
+                [(n, f32) for n in ("ln_eps", "ln2_eps")] +
+                [(n, vp) for n in ("key_mask", "w_qkv", "b_qkv", "w_ao", "b_ao", "ln1_gamma", "ln1_beta", "w_ff1", "b_ff1", "w_ff2", "b_ff2",
+                                   "ln2_gamma", "ln2_beta", "prefix_qkv", "cache_k", "cache_v", "x", "x_res")] + [("x_res_bf16", i32)] +
+                [(n, vp) for n in ("qkv", "cx", "pre1", "x1", "x1_32", "h", "pre2", "ln_stats", "y", "y32", "attn_partials")] +
+                [("attn_partials_capacity", i64)])
+
+
 P = C.POINTER
 _SIGS = {
     "lav_last_error": (C.c_char_p, []),
@@ -147,6 +162,13 @@ _SIGS = {
     "lav_cast_bf16_to_f32": (i32, [vp, i64, vp, vp]),
     "lav_zero_blocks": (i32, [vp, vp, vp, i64, i32]),
     "lav_fill_droppath": (i32, [vp, i32, i32, vp, u32, vp]),
+    # caption decoding (csrc/decode.hip, csrc/stages.cpp)
+    "lav_gemm_skinny_bf16": (i32, [vp, i32, i32, i32, vp, i64, vp, i64, vp, i32, vp, i64, i32, vp, i64]),
+    "lav_attention_decode_splits": (i32, [P(AttnDecodeDesc)]),
+    "lav_attention_decode": (i32, [vp, P(AttnDecodeDesc)]),
+    "lav_text_embed_rows_fwd": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp]),
+    "lav_greedy_step": (i32, [vp, i32, i32, vp, i64, vp, i64, i32, f32, vp, vp, vp, i64, i64, vp, i64]),
+    "lav_bert_layer_decode": (i32, [vp, P(BertLayerDecodeDesc)]),
     # fp32-I/O validation mode (csrc/validate.hip)
     "lav_v_gemm_f32": (i32, [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i32, vp, i64]),
     "lav_v_attention_f32": (i32, [vp, P(AttnDesc), vp, vp, vp]),

@@ -1,0 +1,259 @@
+"""Caption generation for LAVENDER_Captioning (model_for_captioning.py:139-500, driven by main_caption.py:98-125): greedy and
+sampled decoding without beam search.
+
+Under the seq2seq mask video rows never see text and text row i never sees rows after i, so the fusion encoder's keys and
+values can be cached exactly:
+  * prefix, once per batch: the video rows alone through every layer (lav_bert_layer_fwd, eval); each layer's qkv buffer is kept,
+    its k | v columns are the video part of that layer's cache (read in place by the decode attention);
+  * step t: two rows per clip -- the token chosen at step t - 1 (position t - 1; its k / v were those of [MASK] the step before and are
+    recomputed) and a fresh [MASK] at position t -- through every layer (lav_bert_layer_decode); the real token's k / v go to the
+    per-layer text cache (B, heads, max_len, 64); the MLM head runs on the B [MASK] rows only, with fp32 logits.
+Greedy steps choose the token on the device (lav_greedy_step): a whole greedy generation makes no host synchronisation until
+the final copy.  Sampling (do_sample) draws with torch ops on the fp32 [MASK] logits, as the reference does.
+LAV_CAP_KV=0 runs the reference's literal loop instead: the whole fusion encoder over Lv + cur_len + 1 rows for every token."""
+import os
+
+import torch
+
+from . import engine as E
+from . import hip as K
+
+KV = os.environ.get("LAV_CAP_KV", "1") != "0"
+
+
+class GenConfig:
+    """The generation arguments generate() reads from args (model_for_captioning.py:150-162), checked."""
+
+    def __init__(self, args, X):
+        get = args.get if hasattr(args, "get") else (lambda k, d: getattr(args, k, d))
+        self.max_len = int(get("max_gen_length", 20))
+        self.do_sample = bool(get("do_sample", False))
+        self.temperature = float(get("gen_temperature", 1.0))
+        self.top_k = int(get("top_k", 0))
+        self.top_p = float(get("top_p", 1.0))
+        self.penalty = float(get("repetition_penalty", 1.0))
+        for k in ("num_beams", "num_keep_best", "num_return_sequences", "num_fsm_states"):
+            if int(get(k, 1)) != 1:
+                raise NotImplementedError(f"caption generation: {k} = {get(k, 1)}; only 1 is supported (the reference has no beam search: "
+                                          "with num_beams > 1 it expands the video features but not the ids and fails)")
+        if self.max_len > X:
+            raise ValueError(f"caption generation: max_gen_length {self.max_len} exceeds the text length {X} of the batch (the reference slices "
+                             "its (Lv + X)-wide seq2seq mask to Lv + max_gen_length rows)")
+        if self.max_len < 2:
+            raise ValueError(f"caption generation: max_gen_length {self.max_len} < 2 generates nothing")
+
+
+# ---- host pieces shared by every path (pure torch) ---------------------------------------------------------------------------
+def apply_repetition_penalty(logits, prev_ids, penalty):
+    """in place: every distinct id of prev_ids[b] scales logits[b, id] once -- multiplied when negative, divided otherwise"""
+    if penalty == 1.0:
+        return logits
+    v = logits.gather(1, prev_ids)
+    logits.scatter_(1, prev_ids, torch.where(v < 0, v * penalty, v / penalty))      # duplicates write the same value
+    return logits
+
+
+def top_k_top_p_filtering(logits, top_k=0, top_p=1.0, filter_value=-float("inf")):
+    """the reference's filter (model_for_captioning.py:502-534, min_tokens_to_keep 1), in place"""
+    if top_k > 0:
+        top_k = min(top_k, logits.size(-1))
+        logits[logits < torch.topk(logits, top_k)[0][..., -1, None]] = filter_value
+    if top_p < 1.0:
+        srt, idx = torch.sort(logits, descending=True)
+        drop = torch.cumsum(torch.softmax(srt, dim=-1), dim=-1) > top_p
+        drop[..., 1:] = drop[..., :-1].clone()
+        drop[..., 0] = False
+        logits[drop.scatter(1, idx, drop)] = filter_value
+    return logits
+
+
+def choose_tokens(logits, prev_ids, cfg, generator=None):
+    """one step of _generate_no_beam_search on fp32 logits (B, V): penalty, then temperature + filtering + multinomial or argmax;
+    returns (token, log_softmax score of the token under the logits it was drawn from)"""
+    logits = apply_repetition_penalty(logits, prev_ids, cfg.penalty)
+    if cfg.do_sample:
+        if cfg.temperature != 1.0:
+            logits = logits / cfg.temperature
+        logits = top_k_top_p_filtering(logits, cfg.top_k, cfg.top_p)
+        tok = torch.multinomial(torch.softmax(logits, dim=-1), num_samples=1, generator=generator).squeeze(1)
+    else:
+        tok = torch.argmax(logits, dim=-1)
+    score = torch.log_softmax(logits, dim=-1).gather(1, tok[:, None]).squeeze(1)
+    return tok, score
+
+
+def record_step(ids, cur, tok, score, state, pad_id, eos_id):
+    """the bookkeeping of one step: finished rows emit [PAD] and do not count; a row finishes on [SEP].  state = (unfinished int32,
+    score_sum fp32, count fp32), updated in place (what lav_greedy_step does on the device)."""
+    unf, ssum, cnt = state
+    u = unf.bool()
+    t = torch.where(u, tok, torch.full_like(tok, pad_id))
+    ids[:, cur] = t
+    ssum += torch.where(u, score.float(), torch.zeros_like(ssum))
+    cnt += u.float()
+    unf.copy_((u & (t != eos_id)).to(unf.dtype))
+    return t
+
+
+def finish_generation(ids, cur_len, max_len, unfinished, score_sum, count, pad_id, eos_id):
+    """end of _generate_no_beam_search: ids (B, >= cur_len) holds [CLS] + the generated tokens in columns < cur_len.  When the loop ran
+    to max_len, still-unfinished rows get [SEP] in the last column; the score is the mean over the counted steps; ids are padded with
+    [PAD] to max_len.  Returns (ids (B, 1, max_len) int64, logprob (B, 1))."""
+    B = ids.shape[0]
+    out = torch.full((B, max_len), pad_id, dtype=torch.long, device=ids.device)
+    out[:, :cur_len] = ids[:, :cur_len]
+    if cur_len == max_len:
+        out[:, -1] = torch.where(unfinished.bool(), torch.full_like(out[:, -1], eos_id), out[:, -1])
+    logprob = score_sum.float() / count.float()
+    return out.unsqueeze(1), logprob.unsqueeze(1)
+
+
+# ---- the key / value cached decoder --------------------------------------------------------------------------------------------
+class KVDecoder:
+    """Buffers and launches of the cached path for one batch of at most KV_MAX_CLIPS clips: the prefix pass in the constructor, then step(t)
+    for t = 1 .. max_len - 1."""
+
+    def __init__(self, model, feat_img, mask_img, max_len):
+        self.m = model
+        arena = model.arena()
+        dev = feat_img.device
+        B, Lv, H = feat_img.shape
+        assert B <= KV_MAX_CLIPS, f"KVDecoder: {B} clips, at most {KV_MAX_CLIPS} at once (caption_decode.generate splits larger batches)"
+        layers = model.trsfr.layer
+        heads = layers[0].num_heads
+        F = layers[0].intermediate.dense.weight.shape[0]
+        self.B, self.Lv, self.H, self.heads, self.F, self.max_len = B, Lv, H, heads, F, max_len
+        self.km = mask_img.to(torch.int32).contiguous()
+        e, bf16, f32 = torch.empty, torch.bfloat16, torch.float32
+        R = 2 * B
+        # prefix: the video rows through every layer, each layer's qkv kept
+        x = feat_img.reshape(B * Lv, H).contiguous()
+        resln = None
+        self.prefix_qkv, consts = [], []
+        for lyr in layers:
+            wqkv16, _, _ = arena.fused_view(lyr.attention.self.query.weight, 3 * H)
+            _, _, bqkv = arena.fused_view(lyr.attention.self.query.bias, 3 * H)
+            c = E.BertLayerFn._layer_consts(lyr, arena, wqkv16, bqkv)
+            x, resln, qkv = E.bert_layer_eval_c(x, resln, lyr, c, self.km, B, Lv)
+            self.prefix_qkv.append(qkv)
+            consts.append(c)
+        # per-layer text caches and the step's workspaces
+        self.cache = [(torch.zeros((B, heads, max_len, 64), dtype=bf16, device=dev), torch.zeros((B, heads, max_len, 64), dtype=bf16, device=dev))
+                      for _ in layers]
+        self.emb = e((R, H), dtype=bf16, device=dev)
+        self.qkv, self.cx, self.x1, self.h = e((R, 3 * H), dtype=bf16, device=dev), e((R, H), dtype=bf16, device=dev), e((R, H), dtype=bf16, device=dev), \
+            e((R, F), dtype=bf16, device=dev)
+        self.pre1, self.pre2, self.x1_32 = e((R, H), dtype=f32, device=dev), e((R, H), dtype=f32, device=dev), e((R, H), dtype=f32, device=dev)
+        self.stats = e((2 * R,), dtype=f32, device=dev)
+        self.y = [e((R, H), dtype=bf16, device=dev) for _ in range(2)]
+        self.y32 = [e((R, H), dtype=f32, device=dev) for _ in range(2)]
+        # the key-split partials of the decode attention: sized for the step that needs the most splits (lav_attention_decode also checks the
+        # capacity it is given and refuses a smaller workspace)
+        splits = max(K.attention_decode_splits(K.attn_decode_desc(B, heads, 2, Lv, t - 1, 1, max_len, None, None, None, None, None, None))
+                     for t in range(1, max_len))
+        self.partials = e((B * heads * splits * 2 * 66,), dtype=f32, device=dev)
+        self.descs = []
+        for i, c in enumerate(consts):
+            p = c["params"]
+            d = K.L.BertLayerDecodeDesc(B, 2, H, heads, F, Lv, 0, 1, max_len, c["eps"], c["eps2"], self.km.data_ptr(), *p,
+                                        self.prefix_qkv[i].data_ptr(), self.cache[i][0].data_ptr(), self.cache[i][1].data_ptr(),
+                                        0, 0, 0, self.qkv.data_ptr(), self.cx.data_ptr(), self.pre1.data_ptr(), self.x1.data_ptr(),
+                                        self.x1_32.data_ptr(), self.h.data_ptr(), self.pre2.data_ptr(), self.stats.data_ptr(),
+                                        self.y[i % 2].data_ptr(), self.y32[i % 2].data_ptr(), self.partials.data_ptr(), self.partials.numel())
+            d.x = self.emb.data_ptr() if i == 0 else self.y[(i - 1) % 2].data_ptr()
+            d.x_res = self.emb.data_ptr() if i == 0 else self.y32[(i - 1) % 2].data_ptr()
+            d.x_res_bf16 = 1 if i == 0 else 0
+            self.descs.append(d)
+        self.last_y = self.y[(len(layers) - 1) % 2]
+        # head
+        head = model.fc_mtm.predictions
+        self.V = head.decoder.weight.shape[0]
+        self.t1, self.tn = e((B, H), dtype=bf16, device=dev), e((B, H), dtype=bf16, device=dev)
+        self.logits = e((B, self.V), dtype=f32, device=dev)
+        # step inputs: the known token (written by the greedy step) and [MASK], positions t - 1 and t
+        self.step_ids = torch.full((B, 2), model.mask_token_id, dtype=torch.long, device=dev)
+        self.step_ids[:, 0] = model.cls_token_id
+        tt = torch.arange(max_len, dtype=torch.int32, device=dev)
+        self.pos = torch.stack([tt - 1, tt], 1)[:, None, :].expand(max_len, B, 2).contiguous()
+
+    def step(self, t):
+        """the [MASK]-row logits (B, V) fp32 of step t (cur_len = t): the known token at position t - 1 is step_ids[:, 0]"""
+        m = self.m
+        emb = m.enc_txt.emb_txt
+        K.text_embed_rows(self.step_ids, self.pos[t], self.H, emb.word_embeddings.weight.data, emb.position_embeddings.weight.data,
+                          emb.token_type_embeddings.weight.data, emb.LayerNorm.weight.data, emb.LayerNorm.bias.data, emb.LayerNorm.eps, self.emb)
+        for d in self.descs:
+            d.n_cached = t - 1
+            K.bert_layer_decode(d)
+        tr, dec = m.fc_mtm.predictions.transform, m.fc_mtm.predictions.decoder
+        ymask = self.last_y.view(self.B, 2, self.H)[:, 1]
+        K.gemm_skinny(ymask, E.W16(tr.dense.weight), self.B, self.H, self.H, self.t1, K.SKINNY_GELU, bias=tr.dense.bias.data)
+        K.layernorm_fwd(self.t1, self.B, self.H, tr.LayerNorm.weight.data, tr.LayerNorm.bias.data, tr.LayerNorm.eps, out=self.tn, want_stats=False)
+        K.gemm_skinny(self.tn, E.W16(dec.weight), self.B, self.V, self.H, self.logits, K.SKINNY_F32, bias=dec.bias.data)
+        return self.logits
+
+
+def recompute_logits(model, feat_img, mask_img, ids, cur_len):
+    """the reference's step (model_for_captioning.py:96-130, past is None): text [ids[:, :cur_len] ; MASK] at positions 0..cur_len, the whole
+    fusion encoder over Lv + cur_len + 1 rows under the seq2seq mask, the MLM head at the [MASK] row; fp32 (B, V)"""
+    B, Lv, _ = feat_img.shape
+    inp = torch.cat([ids[:, :cur_len], torch.full((B, 1), model.mask_token_id, dtype=torch.long, device=ids.device)], 1)
+    f_txt = model.enc_txt(inp)
+    key_mask = torch.cat([mask_img, torch.ones((B, cur_len + 1), dtype=mask_img.dtype, device=mask_img.device)], 1)
+    hid = model._encode(torch.cat([feat_img, f_txt], 1), key_mask, causal_from=Lv)
+    return model.fc_mtm(hid[:, Lv + cur_len].contiguous()).float()
+
+
+KV_MAX_CLIPS = 32          # the cached path decodes at most this many clips at once: 2 rows per clip through the skinny GEMMs (M <= 64)
+
+
+def generate(model, img, X, cfg, kv=None, generator=None, forced_ids=None, step_logits=None):
+    """(ids (B, 1, max_len), logprob (B, 1)).  forced_ids (B, max_len): teacher forcing (tests; the chosen tokens are replaced by these
+    before the next step); step_logits: a list that receives each step's fp32 [MASK] logits (B, V) before the penalty.  The cached path
+    decodes larger batches in chunks of KV_MAX_CLIPS clips (every clip's caption is independent of the others)."""
+    kv = KV if kv is None else kv
+    B = img.shape[0]
+    if not kv or B <= KV_MAX_CLIPS:
+        return _generate(model, img, X, cfg, kv, generator, forced_ids, step_logits)
+    ids, lps, chunk_steps = [], [], []
+    for s in range(0, B, KV_MAX_CLIPS):
+        st = [] if step_logits is not None else None
+        i, lp = _generate(model, img[s:s + KV_MAX_CLIPS], X, cfg, kv, generator,
+                          None if forced_ids is None else forced_ids[s:s + KV_MAX_CLIPS], st)
+        ids.append(i)
+        lps.append(lp)
+        chunk_steps.append(st)
+    if step_logits is not None:
+        step_logits.extend(torch.cat(parts, 0) for parts in zip(*chunk_steps))
+    return torch.cat(ids, 0), torch.cat(lps, 0)
+
+
+def _generate(model, img, X, cfg, kv, generator, forced_ids, step_logits):
+    pad_id, eos_id, cls_id = model.pad_token_id, model.sep_token_id, model.cls_token_id
+    feat_img, mask_img = model.enc_img(img)
+    B, dev, L = feat_img.shape[0], feat_img.device, cfg.max_len
+    ids = torch.full((B, L), pad_id, dtype=torch.long, device=dev)
+    ids[:, 0] = cls_id
+    state = (torch.ones(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.float32, device=dev),
+             torch.zeros(B, dtype=torch.float32, device=dev))
+    dec = KVDecoder(model, feat_img, mask_img, L) if kv else None
+    cur = 1
+    while cur < L:
+        logits = dec.step(cur) if kv else recompute_logits(model, feat_img, mask_img, ids, cur)
+        if step_logits is not None:
+            step_logits.append(logits.clone())
+        if kv and not cfg.do_sample:
+            K.greedy_step(logits, dec.V, ids, cur, cfg.penalty, *state, pad_id, eos_id, next_ids=dec.step_ids, ld_next=2)
+        else:
+            tok, score = choose_tokens(logits.clone() if kv else logits, ids[:, :cur], cfg, generator)
+            t = record_step(ids, cur, tok, score, state, pad_id, eos_id)
+            if kv:
+                dec.step_ids[:, 0] = t
+        if forced_ids is not None:
+            ids[:, cur] = forced_ids[:, cur]
+            if kv:
+                dec.step_ids[:, 0] = forced_ids[:, cur]
+        cur += 1
+        if not kv and int(state[0].max()) == 0:           # the reference's early stop (the cached path runs on: identical outputs)
+            break
+    return finish_generation(ids, cur, L, *state, pad_id, eos_id)

@@ -270,3 +270,34 @@ extern "C" int lav_swin_block_bwd(void* stream, void* side_stream, const lav_swi
                               b->g_ln1_gamma, b->g_ln1_beta, nullptr));
     return LAV_OK;
 }
+
+// One fusion layer over the new rows of a decoding step (model_for_captioning.py:96-130 with a key / value cache): the arithmetic of
+// lav_bert_layer_fwd at eval, on skinny GEMMs and the decode attention.
+extern "C" int lav_bert_layer_decode(void* stream, const lav_bert_layer_decode_desc* d) {
+    LAV_REQUIRE(d, "lav_bert_layer_decode: null descriptor");
+    LAV_REQUIRE(d->B > 0 && d->q_len > 0 && d->B * d->q_len <= 64 && d->hidden > 0 && d->heads > 0 && d->hidden == 64 * d->heads && d->ffn > 0,
+                "lav_bert_layer_decode: B=%d q_len=%d (B * q_len <= 64) hidden=%d heads=%d ffn=%d", d->B, d->q_len, d->hidden, d->heads, d->ffn);
+    LAV_REQUIRE(d->x && d->x_res && d->w_qkv && d->w_ao && d->w_ff1 && d->w_ff2 && d->qkv && d->cx && d->pre1 && d->x1 && d->x1_32 && d->h &&
+                d->pre2 && d->ln_stats && d->y && d->y32, "lav_bert_layer_decode: null buffer");
+    const int R = d->B * d->q_len, H = d->hidden, F = d->ffn;
+    LAV_TRY(lav_gemm_skinny_bf16(stream, R, 3 * H, H, d->x, H, d->w_qkv, H, d->b_qkv, LAV_SKINNY_BF16, nullptr, 0, 0, d->qkv, 3 * H));
+    {
+        lav_attn_decode_desc a;
+        memset(&a, 0, sizeof(a));
+        a.B = d->B; a.heads = d->heads; a.head_dim = 64; a.q_len = d->q_len; a.Lv = d->Lv; a.n_cached = d->n_cached; a.n_append = d->n_append;
+        a.max_len = d->max_len; a.scale = (float)pow(64.0, -0.5);
+        a.prefix_qkv = d->prefix_qkv; a.ld_prefix = 3 * H; a.key_mask = d->key_mask;
+        a.qkv_new = d->qkv; a.ld_new = 3 * H; a.cache_k = d->cache_k; a.cache_v = d->cache_v; a.out = d->cx; a.ldo = H;
+        a.partials = d->attn_partials; a.partials_capacity = d->attn_partials_capacity;
+        LAV_TRY(lav_attention_decode(stream, &a));
+    }
+    LAV_TRY(lav_gemm_skinny_bf16(stream, R, H, H, d->cx, H, d->w_ao, H, d->b_ao, LAV_SKINNY_RES_F32, d->x_res, H, d->x_res_bf16, d->pre1, H));
+    lav_ln_f32 f32io; f32io.x_f32 = 1; f32io.y32 = d->x1_32; f32io.ldy32 = H;
+    LAV_TRY(lav_layernorm_fwd(stream, R, H, d->pre1, H, nullptr, d->ln1_gamma, d->ln1_beta, d->ln_eps, d->x1, H, d->ln_stats, d->ln_stats + R, &f32io));
+    LAV_TRY(lav_gemm_skinny_bf16(stream, R, F, H, d->x1, H, d->w_ff1, H, d->b_ff1, LAV_SKINNY_GELU, nullptr, 0, 0, d->h, F));
+    LAV_TRY(lav_gemm_skinny_bf16(stream, R, H, F, d->h, F, d->w_ff2, F, d->b_ff2, LAV_SKINNY_RES_F32, d->x1_32, H, 0, d->pre2, H));
+    lav_ln_f32 f32o; f32o.x_f32 = 1; f32o.y32 = d->y32; f32o.ldy32 = H;
+    LAV_TRY(lav_layernorm_fwd(stream, R, H, d->pre2, H, nullptr, d->ln2_gamma, d->ln2_beta, d->ln2_eps > 0.f ? d->ln2_eps : d->ln_eps, d->y, H,
+                              d->ln_stats, d->ln_stats + R, &f32o));
+    return LAV_OK;
+}

@@ -845,14 +845,13 @@ class BertLayerFn(torch.autograd.Function):
         return consts
 
     @staticmethod
-    def _forward_c(ctx, x, resln_t, layer, key_mask, n, L, p_hidden, p_attn, want32, causal_from, keep, wqkv16, bqkv):
-        """the same seven launches as the per-kernel path below, enqueued by ONE call of lav_bert_layer_fwd"""
+    def _launch_c(x, resln_t, c, key_mask, n, L, p_hidden, p_attn, seeds, causal_from, keep):
+        """allocate one layer's activations and enqueue lav_bert_layer_fwd on them: (descriptor fields, (qkv, cx, lse, pre1, st1, x1, h_pre, h,
+        pre2, st2, y), residual addresses).  st1 / st2 = (mean, rstd) of the two LayerNorms; lse and h_pre exist only when `keep`."""
         Hd, R = x.shape[1], n * L
-        assert x.shape[0] == R and x.is_contiguous()
         dev, f32 = x.device, torch.float32
-        c = BertLayerFn._layer_consts(layer, layer._arena(), wqkv16, bqkv)
         F = c["ffn"]
-        s_att, s1, s2 = K.next_seed(), K.next_seed(), K.next_seed()
+        s_att = seeds[0]
         e = torch.empty
         qkv, cx, x1, h, y = e((R, 3 * Hd), dtype=bf16, device=dev), e((R, Hd), dtype=bf16, device=dev), e((R, Hd), dtype=bf16, device=dev), \
             e((R, F), dtype=bf16, device=dev), e((R, Hd), dtype=bf16, device=dev)
@@ -868,11 +867,21 @@ class BertLayerFn(torch.autograd.Function):
         else:
             res = (0, 0, 0, 0, 0)
         p1, p2 = st1.data_ptr(), st2.data_ptr()
-        fields = (n, L, Hd, c["heads"], F, float(p_hidden), float(p_attn), c["eps"], s_att, s1, s2, int(causal_from),
+        fields = (n, L, Hd, c["heads"], F, float(p_hidden), float(p_attn), c["eps"]) + tuple(seeds) + (int(causal_from),
                   K._dp(key_mask)) + c["params"] + (x.data_ptr(),) + res + (
                   qkv.data_ptr(), cx.data_ptr(), K._dp(lse), pre1.data_ptr(), p1, p1 + 4 * R, x1.data_ptr(), K._dp(h_pre), h.data_ptr(),
                   pre2.data_ptr(), p2, p2 + 4 * R, y.data_ptr(), int(STREAM_DT == torch.float16), c["eps2"])
         K.bert_layer_fwd(fields)
+        return fields, (qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, y), res
+
+    @staticmethod
+    def _forward_c(ctx, x, resln_t, layer, key_mask, n, L, p_hidden, p_attn, want32, causal_from, keep, wqkv16, bqkv):
+        """the same seven launches as the per-kernel path below, enqueued by ONE call of lav_bert_layer_fwd"""
+        assert x.shape[0] == n * L and x.is_contiguous()
+        c = BertLayerFn._layer_consts(layer, layer._arena(), wqkv16, bqkv)
+        s_att, s1, s2 = K.next_seed(), K.next_seed(), K.next_seed()
+        fields, (qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, y), res = BertLayerFn._launch_c(
+            x, resln_t, c, key_mask, n, L, p_hidden, p_attn, (s_att, s1, s2), causal_from, keep)
         mean2, rstd2 = st2[0], st2[1]
         if keep:
             ctx.layer, ctx.seeds, ctx.p = layer, (s1, s2), p_hidden
@@ -969,6 +978,15 @@ class BertLayerFn(torch.autograd.Function):
         grp.launch(x.device)
         dx = K.gemm(0, dqkv, W16T(att_m.query.weight), R, Hd, 3 * Hd, residual=d_pre1)
         return None, dx, None, None, None, None, None, None, None, None, None, None
+
+
+def bert_layer_eval_c(x, resln_t, layer, c, key_mask, n, L):
+    """BertLayerFn._forward_c at eval (no dropout, nothing kept, causal_from 0, no seeds drawn), returning the layer's qkv too:
+    (y, (pre2, mean2, rstd2, gamma2, beta2) for the next layer's residual, qkv).  The prefix pass of caption decoding (caption_decode.py)."""
+    assert x.shape[0] == n * L and x.is_contiguous()
+    _, (qkv, _, _, _, _, _, _, _, pre2, st2, y), _ = BertLayerFn._launch_c(x, resln_t, c, key_mask, n, L, 0.0, 0.0, (0, 0, 0), 0, False)
+    out = layer.output.LayerNorm
+    return y, (pre2, st2[0], st2[1], out.weight.data, out.bias.data), qkv
 
 
 class MLMHeadFn(torch.autograd.Function):

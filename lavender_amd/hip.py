@@ -649,3 +649,46 @@ def v_text_embed(ids, n, X, Hd, word, pos, type0, gamma, beta, eps, out):
 
 def v_gather_rows(src, src_row, n_rows, Cn, out):
     L.check(L.lib.lav_v_gather_rows_f32(_s(), n_rows, Cn, _p(src), _ld(src), _p(src_row), _p(out), _ld(out)), "lav_v_gather_rows_f32")
+
+
+# ---- caption decoding (csrc/decode.hip) ----------------------------------------------------------------------------------------
+SKINNY_BF16, SKINNY_GELU, SKINNY_RES_F32, SKINNY_F32 = 0, 1, 2, 3
+
+
+def gemm_skinny(x, w, M, N, K, out, epi=SKINNY_BF16, bias=None, residual=None, ldx=None, ldo=None):
+    """out[M, N] = x[M, K] . w[N, K]^T (+ bias, epilogue epi) for M <= 64: lav_gemm_skinny_bf16"""
+    res_bf16 = int(residual is not None and residual.dtype == bf16)
+    L.check(L.lib.lav_gemm_skinny_bf16(_s(), M, N, K, _p(x), ldx or _ld(x), _p(w), _ld(w), _p(bias), epi, _p(residual),
+                                        _ld(residual) if residual is not None else 0, res_bf16, _p(out), ldo or _ld(out)), "lav_gemm_skinny_bf16")
+    return out
+
+
+def attn_decode_desc(B, heads, q_len, Lv, n_cached, n_append, max_len, prefix_qkv, key_mask, qkv_new, cache_k, cache_v, out, partials=None):
+    H = heads * 64
+    return L.AttnDecodeDesc(B, heads, 64, q_len, Lv, n_cached, n_append, max_len, 0.125, _dp(prefix_qkv), 3 * H, _dp(key_mask), _dp(qkv_new),
+                            3 * H, _dp(cache_k), _dp(cache_v), _dp(out), H, _dp(partials), partials.numel() if partials is not None else 0)
+
+
+def attention_decode_splits(desc):
+    return int(L.lib.lav_attention_decode_splits(C.byref(desc)))
+
+
+def attention_decode(desc):
+    L.check(L.lib.lav_attention_decode(_s(), C.byref(desc)), "lav_attention_decode")
+
+
+def text_embed_rows(ids, pos_ids, Hd, word, pos, type0, gamma, beta, eps, out):
+    n = ids.numel()
+    L.check(L.lib.lav_text_embed_rows_fwd(_s(), n, Hd, _p(ids), _p(pos_ids), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta), eps, _p(out)),
+            "lav_text_embed_rows_fwd")
+    return out
+
+
+def greedy_step(logits, V, ids, cur, penalty, unfinished, score_sum, count, pad_id, eos_id, next_ids=None, ld_next=0):
+    B = logits.shape[0]
+    L.check(L.lib.lav_greedy_step(_s(), B, V, _p(logits), logits.stride(0), _p(ids), ids.stride(0), cur, float(penalty), _p(unfinished),
+                                  _p(score_sum), _p(count), int(pad_id), int(eos_id), _p(next_ids), ld_next), "lav_greedy_step")
+
+
+def bert_layer_decode(desc):
+    L.check(L.lib.lav_bert_layer_decode(_s(), C.byref(desc)), "lav_bert_layer_decode")
