@@ -599,6 +599,61 @@ typedef struct lav_bert_layer_decode_desc {
 int lav_bert_layer_decode(void* stream, const lav_bert_layer_decode_desc* d);
 
 /* ---------------------------------------------------------------------------------------------
+ * Beam search on the cached decoder (csrc/decode.hip; Oscar / SwinBERT's _generate_beam_search + BeamHypotheses, HF 2.x).  The rows of a
+ * step are beams x clips, row r = clip * beams + beam.  Everything stays on the device: a whole generation needs no host synchronisation.
+ *
+ * lav_attention_decode_beam / lav_bert_layer_decode_beam: lav_attention_decode / lav_bert_layer_decode with d->B = clips * beams row groups
+ * (text cache, new rows and outputs per row group) whose video keys [0, Lv) and key mask are those of clip b / beams, read in place from a
+ * prefix pass over the clips alone (prefix_qkv (clips * Lv, 3 hidden), key_mask (clips, Lv)).  beams 1 is the plain entry, bit for bit. */
+#define LAV_BEAM_MAX 8
+int lav_attention_decode_beam(void* stream, const lav_attn_decode_desc* d, int beams);
+int lav_bert_layer_decode_beam(void* stream, const lav_bert_layer_decode_desc* d, int beams);
+
+/* Beam step, one workgroup per row of fp32 logits (rows, V), row pitch ld, in one pass over the row:
+ *   penalty != 1: every distinct id of ids[r, 0 .. cur) scales its logit IN PLACE (the rule of lav_greedy_step);
+ *   the row's top 2 * beams logits (value descending, lower index on a tie) and its log-sum-exp;
+ *   cand_score[r, j] = log_softmax(row)[word] + beam_scores[r], cand_word[r, j] = word  (rows, 2 * beams) fp32 / int32. */
+int lav_beam_step(void* stream, int rows, int beams, int V, float* logits, long ld, const int64_t* ids, long ld_ids, int cur, float penalty,
+                  const float* beam_scores, float* cand_score, int32_t* cand_word);
+
+/* Beam select, one workgroup per clip, for step cur (1 <= cur < max_len).  The clip's beams * 2 * beams candidates of lav_beam_step are
+ * ordered by score descending, flat index beam * V + word ascending on a tie; the first 2 * beams are the clip's candidates.  Then:
+ *   a clip not done becomes done when it holds `keep` hypotheses and early_stopping, or worst >= best candidate / max_norm;
+ *   a clip not done walks its candidates: a [SEP] word (eos_id), or any word when cur + 1 == max_len, offers the hypothesis (the parent's
+ *   ids [0, cur), normalised score s = score / cur_norm), kept while fewer than `keep` are held or when s > worst; on overflow the lowest s
+ *   goes (the earliest insertion among equals) and worst is the new minimum, a plain add sets worst = min(worst, s); any other word is a
+ *   next beam (parent, word, score); the walk stops at `beams` next beams;
+ *   beams of a done clip (and the unfilled ones of the last step) keep their row, score and ids and get [PAD] (pad_id).
+ * Writes ids[r, 0 .. cur) (gathered from the parent) and ids[r, cur] = word, next_ids[r * ld_next] = word (when not NULL), parent[r] (global
+ * row), beam_scores[r]; a kept hypothesis row of hyp_ids (clips, keep, max_len) is the parent's ids, [SEP], then [PAD], with hyp_score (clips,
+ * keep), hyp_seq (its insertion number), state (clips, 3) int32 = (held, done, insertions so far) and worst (clips).  Start state: beam
+ * scores 0 for beam 0 and -1e9 for the others, state 0, worst 1e9.  cur_norm = cur ** length_penalty and max_norm = max_len ** length_penalty
+ * (fp32; the divisions are IEEE fp32). */
+typedef struct lav_beam_select_desc {
+    int clips, beams, keep, V, cur, max_len, early_stopping;
+    float cur_norm, max_norm;
+    int64_t eos_id, pad_id;
+    const float* cand_score; const int32_t* cand_word;     /* (clips * beams, 2 * beams) */
+    float* beam_scores;                                    /* (clips * beams) */
+    int64_t* ids; long ld_ids;                             /* (clips * beams, >= max_len) */
+    int64_t* next_ids; long ld_next;
+    int32_t* parent;                                       /* (clips * beams) */
+    int64_t* hyp_ids; float* hyp_score; int32_t* hyp_seq; int32_t* state; float* worst;
+} lav_beam_select_desc;
+int lav_beam_select(void* stream, const lav_beam_select_desc* d);
+
+/* Re-parenting of the text caches of every layer in one launch: dst_x[l][r, h, 0 .. n_pos) = src_x[l][parent[r], h, 0 .. n_pos) for x = k, v,
+ * caches (rows, heads, max_len, 64) bf16, 16-byte aligned.  A parent outside [0, rows) copies the row itself. */
+#define LAV_REPARENT_MAX_LAYERS 24
+typedef struct lav_beam_reparent_desc {
+    int layers, rows, heads, n_pos, max_len;
+    const int32_t* parent;
+    const void* src_k[LAV_REPARENT_MAX_LAYERS]; const void* src_v[LAV_REPARENT_MAX_LAYERS];
+    void* dst_k[LAV_REPARENT_MAX_LAYERS]; void* dst_v[LAV_REPARENT_MAX_LAYERS];
+} lav_beam_reparent_desc;
+int lav_beam_reparent(void* stream, const lav_beam_reparent_desc* d);
+
+/* ---------------------------------------------------------------------------------------------
  * Process-wide probe switches: environment variables read ONCE by the library on first use (not part of the contract; every setting
  * computes the same results up to fp32 summation order unless stated).  They exist so that tools/ and profiles/ can A/B a kernel
  * choice on one box.

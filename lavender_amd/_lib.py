@@ -111,6 +111,21 @@ class BertLayerDecodeDesc(C.Structure):    # struct lav_bert_layer_decode_desc
                 [("attn_partials_capacity", i64)])
 
 
+class BeamSelectDesc(C.Structure):         # struct lav_beam_select_desc
+    _fields_ = ([(n, i32) for n in ("clips", "beams", "keep", "V", "cur", "max_len", "early_stopping")] + [(n, f32) for n in ("cur_norm", "max_norm")] +
+                [(n, i64) for n in ("eos_id", "pad_id")] +
+                [("cand_score", vp), ("cand_word", vp), ("beam_scores", vp), ("ids", vp), ("ld_ids", i64), ("next_ids", vp), ("ld_next", i64),
+                 ("parent", vp), ("hyp_ids", vp), ("hyp_score", vp), ("hyp_seq", vp), ("state", vp), ("worst", vp)])
+
+
+REPARENT_MAX_LAYERS = 24                    # LAV_REPARENT_MAX_LAYERS
+
+
+class BeamReparentDesc(C.Structure):       # struct lav_beam_reparent_desc
+    _fields_ = ([(n, i32) for n in ("layers", "rows", "heads", "n_pos", "max_len")] + [("parent", vp)] +
+                [(n, vp * REPARENT_MAX_LAYERS) for n in ("src_k", "src_v", "dst_k", "dst_v")])
+
+
 P = C.POINTER
 _SIGS = {
     "lav_last_error": (C.c_char_p, []),
@@ -169,6 +184,12 @@ _SIGS = {
     "lav_text_embed_rows_fwd": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp]),
     "lav_greedy_step": (i32, [vp, i32, i32, vp, i64, vp, i64, i32, f32, vp, vp, vp, i64, i64, vp, i64]),
     "lav_bert_layer_decode": (i32, [vp, P(BertLayerDecodeDesc)]),
+    # beam search (csrc/decode.hip, csrc/stages.cpp)
+    "lav_attention_decode_beam": (i32, [vp, P(AttnDecodeDesc), i32]),
+    "lav_bert_layer_decode_beam": (i32, [vp, P(BertLayerDecodeDesc), i32]),
+    "lav_beam_step": (i32, [vp, i32, i32, i32, vp, i64, vp, i64, i32, f32, vp, vp, vp]),
+    "lav_beam_select": (i32, [vp, P(BeamSelectDesc)]),
+    "lav_beam_reparent": (i32, [vp, P(BeamReparentDesc)]),
     # fp32-I/O validation mode (csrc/validate.hip)
     "lav_v_gemm_f32": (i32, [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i32, vp, i64]),
     "lav_v_attention_f32": (i32, [vp, P(AttnDesc), vp, vp, vp]),

@@ -3,8 +3,8 @@
 Captioning is MLM under a sequence-to-sequence attention mask (model.py:208-218): every position sees the video tokens,
 a text position additionally sees the text up to itself, video positions see no text.  The mask is not materialised as a
 (B, L, L) tensor on the device path: the fusion attention kernels take (key mask, number of prefix keys)
-(lav_attn_desc.causal_from).  Generation (greedy and sampled decoding, model_for_captioning.py:139-500; the reference has no beam
-search) runs on a key / value cache of the fusion encoder: lavender_amd/caption_decode.py."""
+(lav_attn_desc.causal_from).  Generation (greedy, sampled and beam-search decoding, model_for_captioning.py:139-500) runs on a key / value
+cache of the fusion encoder: lavender_amd/caption_decode.py."""
 from collections import defaultdict
 
 import torch
@@ -35,19 +35,22 @@ class LAVENDER_Captioning(LAVENDER_Base):
 
     def generate(self, batch, generator=None):
         """model_for_captioning.py:139-240 + _generate_no_beam_search (num_beams 1): (ids (B, 1, max_gen_length) int64 starting with [CLS],
-        logprob (B, 1)).  The input text matters only through its length; it is not embedded.  Runs without autograd and in eval mode
+        logprob (B, 1)); num_beams > 1: beam search (caption_decode.generate_beam), (ids (B, num_keep_best, max_gen_length), logprob (B,
+        num_keep_best)), the hypotheses best first.  The input text matters only through its length; it is not embedded.  Runs without autograd and in eval mode
         (model.training is restored afterwards); parameters and gradients are not touched.  `generator`: optional torch.Generator of the
         sampling draws."""
         from . import caption_decode as CD
         batch = defaultdict(lambda: None, batch)
         if batch["prompt"] is not None and getattr(self.args, "enable_prompt", False):
             raise NotImplementedError("task tokens / prompts are outside the built paths")
-        cfg = CD.GenConfig(self.args, batch["txt"].shape[1])
+        cfg = CD.make_config(self.args, batch["txt"].shape[1])
         was_training = self.training
         try:
             self.eval()
             with torch.no_grad():
                 self.arena().sync_half_if_stale()
+                if isinstance(cfg, CD.BeamConfig):
+                    return CD.generate_beam(self, batch["img"], batch["txt"].shape[1], cfg)
                 return CD.generate(self, batch["img"], batch["txt"].shape[1], cfg, generator=generator)
         finally:
             self.train(was_training)

@@ -124,10 +124,11 @@ extern "C" int lav_gemm_skinny_bf16(void* stream, int M, int N, int K, const voi
 #define AD_MAXQ 8
 #define AD_HD 64
 
-// key kk of (b, h): [0, Lv) video rows of the prefix qkv; [Lv, Lv + n_cached) text cache; then the q_len new rows
-__device__ __forceinline__ const bf16_t* ad_key(const lav_attn_decode_desc& d, int b, int h, int kk, int which /* 1 k, 2 v */) {
+// key kk of row group b, head h: [0, Lv) video rows of the prefix qkv (those of clip b / beams: the beams of a clip share them in place);
+// [Lv, Lv + n_cached) text cache; then the q_len new rows
+__device__ __forceinline__ const bf16_t* ad_key(const lav_attn_decode_desc& d, int beams, int b, int h, int kk, int which /* 1 k, 2 v */) {
     const int H = d.heads * AD_HD;
-    if (kk < d.Lv) return (const bf16_t*)d.prefix_qkv + ((long)b * d.Lv + kk) * d.ld_prefix + which * H + h * AD_HD;
+    if (kk < d.Lv) return (const bf16_t*)d.prefix_qkv + ((long)(b / beams) * d.Lv + kk) * d.ld_prefix + which * H + h * AD_HD;
     kk -= d.Lv;
     if (kk < d.n_cached)
         return (const bf16_t*)(which == 1 ? d.cache_k : d.cache_v) + (((long)b * d.heads + h) * d.max_len + kk) * AD_HD;
@@ -135,7 +136,7 @@ __device__ __forceinline__ const bf16_t* ad_key(const lav_attn_decode_desc& d, i
     return (const bf16_t*)d.qkv_new + ((long)b * d.q_len + kk) * d.ld_new + which * H + h * AD_HD;
 }
 
-__global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(lav_attn_decode_desc d, int chunk) {
+__global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(lav_attn_decode_desc d, int chunk, int beams) {
     extern __shared__ float sh[];
     float* q = sh;                                   // [AD_MAXQ][64] (scaled)
     float* s = q + AD_MAXQ * AD_HD;                  // [q_len][chunk] scores, then probabilities
@@ -167,10 +168,10 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(lav_attn_decode
         const int kk = base + (tid >> 3);
         const bool live = kk < k1;
         float kf[8];
-        if (live) unpack8(*(const uint4*)(ad_key(d, b, h, kk, 1) + part * 8), kf);
+        if (live) unpack8(*(const uint4*)(ad_key(d, beams, b, h, kk, 1) + part * 8), kf);
         else for (int e = 0; e < 8; ++e) kf[e] = 0.f;
         bool vis_video = true;
-        if (live && kk < d.Lv && d.key_mask) vis_video = d.key_mask[(long)b * d.Lv + kk] != 0;
+        if (live && kk < d.Lv && d.key_mask) vis_video = d.key_mask[(long)(b / beams) * d.Lv + kk] != 0;
         for (int j = 0; j < d.q_len; ++j) {
             float p = 0.f;
 #pragma unroll
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(lav_attn_decode
 #pragma unroll
     for (int j = 0; j < AD_MAXQ; ++j) acc[j] = 0.f;
     for (int k = wave; k < nk; k += 4) {
-        const float v = bf2f(ad_key(d, b, h, k0 + k, 2)[lane]);
+        const float v = bf2f(ad_key(d, beams, b, h, k0 + k, 2)[lane]);
 #pragma unroll
         for (int j = 0; j < AD_MAXQ; ++j)
             if (j < d.q_len) acc[j] = fmaf(s[j * chunk + k], v, acc[j]);
@@ -267,7 +268,7 @@ extern "C" int lav_attention_decode_splits(const lav_attn_decode_desc* d) {
     return ad_splits(d, &chunk);
 }
 
-extern "C" int lav_attention_decode(void* stream, const lav_attn_decode_desc* d) {
+static int attention_decode(void* stream, const lav_attn_decode_desc* d, int beams) {
     LAV_REQUIRE(d, "lav_attention_decode: null descriptor");
     LAV_REQUIRE(d->head_dim == AD_HD && d->B > 0 && d->heads > 0 && d->q_len >= 1 && d->q_len <= AD_MAXQ && d->Lv >= 0 && d->n_cached >= 0 &&
                 d->n_append >= 0 && d->n_append <= d->q_len && d->n_cached + d->n_append <= d->max_len,
@@ -286,13 +287,21 @@ extern "C" int lav_attention_decode(void* stream, const lav_attn_decode_desc* d)
     }
     const size_t lds = (size_t)(AD_MAXQ * AD_HD + d->q_len * chunk + 4 * d->q_len * AD_HD) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(attn_decode_kernel, dim3(d->B * d->heads, splits), dim3(AD_THREADS), lds, s, *d, chunk);
+    hipLaunchKernelGGL(attn_decode_kernel, dim3(d->B * d->heads, splits), dim3(AD_THREADS), lds, s, *d, chunk, beams);
     if (int rc = lav_check_launch("lav_attention_decode")) return rc;
     if (splits > 1) {
         hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(d->B * d->heads), dim3(AD_THREADS), 0, s, *d, splits);
         return lav_check_launch("lav_attention_decode (combine)");
     }
     return LAV_OK;
+}
+
+extern "C" int lav_attention_decode(void* stream, const lav_attn_decode_desc* d) { return attention_decode(stream, d, 1); }
+
+extern "C" int lav_attention_decode_beam(void* stream, const lav_attn_decode_desc* d, int beams) {
+    LAV_REQUIRE(d && beams >= 1 && beams <= LAV_BEAM_MAX && d->B % beams == 0, "lav_attention_decode_beam: beams=%d (1..%d) must divide B=%d", beams,
+                LAV_BEAM_MAX, d ? d->B : 0);
+    return attention_decode(stream, d, beams);
 }
 
 // ---- embeddings of single rows --------------------------------------------------------------------------------------------
@@ -409,4 +418,233 @@ extern "C" int lav_greedy_step(void* stream, int B, int V, float* logits, long l
     hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, V, logits, ld, ids, ld_ids, cur, penalty,
                        unfinished, score_sum, count, pad_id, eos_id, next_ids, ld_next);
     return lav_check_launch("lav_greedy_step");
+}
+
+// ---- beam search ---------------------------------------------------------------------------------------------------------------
+// The beam search of Oscar / SwinBERT's _generate_beam_search + BeamHypotheses (HF 2.x) on the device: no host synchronisation per step.
+#define BS_THREADS 256
+#define BS_TOP (2 * LAV_BEAM_MAX)           // the running top list of each thread: 2 * beams candidates per row at most
+
+// candidate order: value descending, index ascending on a tie
+__device__ __forceinline__ bool bs_better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
+
+// (m, s) = running max and sum of exp(x - m); merge of two such pairs
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
+    const float M = fmaxf(m, m2);
+    if (M == -INFINITY) return;
+    s = (m == -INFINITY ? 0.f : s * __expf(m - M)) + (m2 == -INFINITY ? 0.f : s2 * __expf(m2 - M));
+    m = M;
+}
+
+__global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(int V, float* logits, long ld, const int64_t* ids, long ld_ids, int cur,
+                                                               float penalty, const float* beam_scores, int k, float* cand_score,
+                                                               int32_t* cand_word) {
+    __shared__ float sv[BS_THREADS / 64], sm[BS_THREADS / 64], ss[BS_THREADS / 64];
+    __shared__ int si[BS_THREADS / 64];
+    __shared__ float top_v[BS_TOP];
+    __shared__ int top_i[BS_TOP];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* x = logits + (long)r * ld;
+    const int64_t* prev = ids + (long)r * ld_ids;
+    if (penalty != 1.f && tid == 0) {
+        // this beam's DISTINCT previous ids once, in place (the rule of lav_greedy_step)
+        for (int c = 0; c < cur; ++c) {
+            const int64_t id = prev[c];
+            bool seen = false;
+            for (int c2 = 0; c2 < c; ++c2) seen |= prev[c2] == id;
+            if (seen || id < 0 || id >= V) continue;
+            const float v = x[id];
+            x[id] = v < 0.f ? v * penalty : v / penalty;
+        }
+        __threadfence();
+    }
+    __syncthreads();
+    // one pass: online max / sum-exp and this thread's top BS_TOP (its indices ascend, so a kept entry never ties a later one from below)
+    float tv[BS_TOP];
+    int ti[BS_TOP];
+#pragma unroll
+    for (int j = 0; j < BS_TOP; ++j) { tv[j] = -INFINITY; ti[j] = 0x7fffffff; }
+    float m = -INFINITY, s = 0.f;
+    for (int i = tid; i < V; i += BS_THREADS) {
+        const float v = x[i];
+        if (v > m) { s = s * __expf(m - v) + 1.f; m = v; }
+        else if (v > -INFINITY) s += __expf(v - m);
+        if (bs_better(v, i, tv[BS_TOP - 1], ti[BS_TOP - 1])) {
+#pragma unroll
+            for (int j = BS_TOP - 1; j > 0; --j) {
+                if (bs_better(v, i, tv[j - 1], ti[j - 1])) { tv[j] = tv[j - 1]; ti[j] = ti[j - 1]; }
+                else if (bs_better(v, i, tv[j], ti[j])) { tv[j] = v; ti[j] = i; }
+            }
+            if (bs_better(v, i, tv[0], ti[0])) { tv[0] = v; ti[0] = i; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+    if (lane == 0) { sm[wave] = m; ss[wave] = s; }
+    // k rounds: the best head of all threads' lists is the next candidate; its owner pops it
+    for (int j = 0; j < k; ++j) {
+        float bv = tv[0];
+        int bi = ti[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(bv, o, 64);
+            const int i2 = __shfl_xor(bi, o, 64);
+            if (bs_better(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+        }
+        if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
+        __syncthreads();
+        bv = sv[0]; bi = si[0];
+        for (int w = 1; w < BS_THREADS / 64; ++w)
+            if (bs_better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
+        if (ti[0] == bi) {
+#pragma unroll
+            for (int q = 0; q < BS_TOP - 1; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
+            tv[BS_TOP - 1] = -INFINITY; ti[BS_TOP - 1] = 0x7fffffff;
+        }
+        if (tid == 0) { top_v[j] = bv; top_i[j] = bi; }
+        __syncthreads();
+    }
+    if (tid < k) {
+        float M = sm[0], S = ss[0];
+        for (int w = 1; w < BS_THREADS / 64; ++w) lse_merge(M, S, sm[w], ss[w]);
+        const int w = min(top_i[tid], V - 1);                   // V >= k: never clamped for finite rows
+        cand_score[(long)r * k + tid] = (top_v[tid] - M) - logf(S) + beam_scores[r];
+        cand_word[(long)r * k + tid] = w;
+    }
+}
+
+extern "C" int lav_beam_step(void* stream, int rows, int beams, int V, float* logits, long ld, const int64_t* ids, long ld_ids, int cur,
+                             float penalty, const float* beam_scores, float* cand_score, int32_t* cand_word) {
+    LAV_REQUIRE(rows > 0 && beams >= 1 && beams <= LAV_BEAM_MAX && V >= 2 * beams && ld >= V && cur >= 1 && cur <= ld_ids,
+                "lav_beam_step: rows=%d beams=%d (1..%d) V=%d ld=%ld cur=%d ld_ids=%ld", rows, beams, LAV_BEAM_MAX, V, ld, cur, ld_ids);
+    LAV_REQUIRE(logits && ids && beam_scores && cand_score && cand_word, "lav_beam_step: null pointer");
+    LAV_REQUIRE(penalty > 0.f, "lav_beam_step: penalty must be positive");
+    hipLaunchKernelGGL(beam_step_kernel, dim3(rows), dim3(BS_THREADS), 0, (hipStream_t)stream, V, logits, ld, ids, ld_ids, cur, penalty,
+                       beam_scores, 2 * beams, cand_score, cand_word);
+    return lav_check_launch("lav_beam_step");
+}
+
+#define SEL_THREADS 128                     // >= LAV_BEAM_MAX * 2 * LAV_BEAM_MAX candidates of a clip
+
+__global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(lav_beam_select_desc d) {
+    extern __shared__ int64_t par_ids[];                     // [beams][cur]: the next beams' parent ids
+    __shared__ float c_s[2 * LAV_BEAM_MAX];
+    __shared__ int c_beam[2 * LAV_BEAM_MAX];
+    __shared__ int64_t c_word[2 * LAV_BEAM_MAX];
+    __shared__ int n_par[LAV_BEAM_MAX];
+    __shared__ int64_t n_word[LAV_BEAM_MAX];
+    __shared__ float n_score[LAV_BEAM_MAX];
+    __shared__ int slot_src[LAV_BEAM_MAX];
+    const int c = blockIdx.x, tid = threadIdx.x, nb = d.beams, k2 = 2 * nb, n = nb * k2, cur = d.cur, L = d.max_len;
+    const long row0 = (long)c * nb;
+    if (tid < k2) { c_s[tid] = -INFINITY; c_beam[tid] = 0; c_word[tid] = d.pad_id; }
+    __syncthreads();
+    // merge: every candidate's rank in the clip (score descending, flat index beam * V + word ascending)
+    if (tid < n) {
+        const float v = d.cand_score[(row0 + tid / k2) * k2 + tid % k2];
+        const long f = (long)(tid / k2) * d.V + d.cand_word[(row0 + tid / k2) * k2 + tid % k2];
+        int rank = 0;
+        for (int o = 0; o < n; ++o) {
+            const float v2 = d.cand_score[(row0 + o / k2) * k2 + o % k2];
+            const long f2 = (long)(o / k2) * d.V + d.cand_word[(row0 + o / k2) * k2 + o % k2];
+            rank += (v2 > v || (v2 == v && f2 < f)) ? 1 : 0;
+        }
+        if (rank < k2) { c_s[rank] = v; c_beam[rank] = tid / k2; c_word[rank] = f - (long)(tid / k2) * d.V; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int* st = d.state + 3 * c;                           // held, done, insertions so far
+        int held = st[0], done = st[1], seq = st[2];
+        float worst = d.worst[c];
+        float* hs = d.hyp_score + (long)c * d.keep;
+        int* hq = d.hyp_seq + (long)c * d.keep;
+        for (int j = 0; j < d.keep; ++j) slot_src[j] = -1;
+        for (int b = 0; b < nb; ++b) { n_par[b] = b; n_word[b] = d.pad_id; n_score[b] = d.beam_scores[row0 + b]; }
+        if (!done && held == d.keep && (d.early_stopping || worst >= c_s[0] / d.max_norm)) done = 1;
+        if (!done) {
+            const bool last = cur + 1 == L;
+            int nn = 0;
+            for (int j = 0; j < k2 && nn < nb; ++j) {
+                if (c_word[j] == d.eos_id || last) {
+                    const float sc = c_s[j] / d.cur_norm;
+                    if (held < d.keep) {                             // a plain add
+                        hs[held] = sc; hq[held] = seq++; slot_src[held] = c_beam[j];
+                        ++held;
+                        worst = fminf(worst, sc);
+                    } else if (sc > worst) {                         // overflow: the lowest score goes, the earliest insertion among equals
+                        int slot = 0;
+                        for (int q = 1; q < d.keep; ++q)
+                            if (hs[q] < hs[slot] || (hs[q] == hs[slot] && hq[q] < hq[slot])) slot = q;
+                        hs[slot] = sc; hq[slot] = seq++; slot_src[slot] = c_beam[j];
+                        worst = hs[0];
+                        for (int q = 1; q < d.keep; ++q) worst = fminf(worst, hs[q]);
+                    }
+                } else {
+                    n_par[nn] = c_beam[j]; n_word[nn] = c_word[j]; n_score[nn] = c_s[j];
+                    ++nn;
+                }
+            }
+        }
+        st[0] = held; st[1] = done; st[2] = seq;
+        d.worst[c] = worst;
+    }
+    __syncthreads();
+    // hypothesis rows written this step: the parent's ids [0, cur), [SEP], then [PAD]
+    for (int j = 0; j < d.keep; ++j) {
+        const int src = slot_src[j];
+        if (src < 0) continue;
+        const int64_t* p = d.ids + (row0 + src) * d.ld_ids;
+        int64_t* h = d.hyp_ids + ((long)c * d.keep + j) * L;
+        for (int q = tid; q < L; q += SEL_THREADS) h[q] = q < cur ? p[q] : (q == cur ? d.eos_id : d.pad_id);
+    }
+    for (int i = tid; i < nb * cur; i += SEL_THREADS) par_ids[i] = d.ids[(row0 + n_par[i / cur]) * d.ld_ids + i % cur];
+    __syncthreads();
+    for (int i = tid; i < nb * cur; i += SEL_THREADS) d.ids[(row0 + i / cur) * d.ld_ids + i % cur] = par_ids[i];
+    if (tid < nb) {
+        const long r = row0 + tid;
+        d.ids[r * d.ld_ids + cur] = n_word[tid];
+        if (d.next_ids) d.next_ids[r * d.ld_next] = n_word[tid];
+        d.parent[r] = (int32_t)(row0 + n_par[tid]);
+        d.beam_scores[r] = n_score[tid];
+    }
+}
+
+extern "C" int lav_beam_select(void* stream, const lav_beam_select_desc* d) {
+    LAV_REQUIRE(d, "lav_beam_select: null descriptor");
+    LAV_REQUIRE(d->clips > 0 && d->beams >= 1 && d->beams <= LAV_BEAM_MAX && d->keep >= 1 && d->keep <= d->beams && d->V >= 2 * d->beams &&
+                d->max_len >= 2 && d->max_len <= 512 && d->cur >= 1 && d->cur < d->max_len && d->ld_ids >= d->max_len,
+                "lav_beam_select: clips=%d beams=%d (1..%d) keep=%d (1..beams) V=%d max_len=%d (2..512) cur=%d ld_ids=%ld", d->clips, d->beams,
+                LAV_BEAM_MAX, d->keep, d->V, d->max_len, d->cur, d->ld_ids);
+    LAV_REQUIRE(d->cur_norm > 0.f && d->max_norm > 0.f, "lav_beam_select: the length normalisers must be positive");
+    LAV_REQUIRE(d->cand_score && d->cand_word && d->beam_scores && d->ids && d->parent && d->hyp_ids && d->hyp_score && d->hyp_seq && d->state &&
+                d->worst, "lav_beam_select: null pointer");
+    const size_t lds = (size_t)d->beams * d->cur * sizeof(int64_t);
+    hipLaunchKernelGGL(beam_select_kernel, dim3(d->clips), dim3(SEL_THREADS), lds, (hipStream_t)stream, *d);
+    return lav_check_launch("lav_beam_select");
+}
+
+// one workgroup per (row, head) of one layer's k or v: positions [0, n_pos) of row parent[row] of the source cache
+__global__ __launch_bounds__(128) void beam_reparent_kernel(lav_beam_reparent_desc d) {
+    const int rh = blockIdx.x, r = rh / d.heads, h = rh % d.heads, layer = blockIdx.y, which = blockIdx.z;
+    int p = d.parent[r];
+    if (p < 0 || p >= d.rows) p = r;
+    const uint4* src = (const uint4*)(which ? d.src_v[layer] : d.src_k[layer]) + ((long)p * d.heads + h) * d.max_len * (AD_HD / 8);
+    uint4* dst = (uint4*)(which ? d.dst_v[layer] : d.dst_k[layer]) + ((long)r * d.heads + h) * d.max_len * (AD_HD / 8);
+    for (int i = threadIdx.x; i < d.n_pos * (AD_HD / 8); i += 128) dst[i] = src[i];
+}
+
+extern "C" int lav_beam_reparent(void* stream, const lav_beam_reparent_desc* d) {
+    LAV_REQUIRE(d, "lav_beam_reparent: null descriptor");
+    LAV_REQUIRE(d->layers >= 1 && d->layers <= LAV_REPARENT_MAX_LAYERS && d->rows > 0 && d->heads > 0 && d->n_pos >= 0 && d->n_pos <= d->max_len,
+                "lav_beam_reparent: layers=%d (1..%d) rows=%d heads=%d n_pos=%d max_len=%d", d->layers, LAV_REPARENT_MAX_LAYERS, d->rows, d->heads,
+                d->n_pos, d->max_len);
+    LAV_REQUIRE(d->parent, "lav_beam_reparent: null parent");
+    for (int l = 0; l < d->layers; ++l) {
+        LAV_REQUIRE(d->src_k[l] && d->src_v[l] && d->dst_k[l] && d->dst_v[l], "lav_beam_reparent: null cache of layer %d", l);
+        LAV_REQUIRE(((uintptr_t)d->src_k[l] | (uintptr_t)d->src_v[l] | (uintptr_t)d->dst_k[l] | (uintptr_t)d->dst_v[l]) % 16 == 0,
+                    "lav_beam_reparent: caches must be 16-byte aligned");
+    }
+    if (d->n_pos == 0) return LAV_OK;
+    hipLaunchKernelGGL(beam_reparent_kernel, dim3(d->rows * d->heads, d->layers, 2), dim3(128), 0, (hipStream_t)stream, *d);
+    return lav_check_launch("lav_beam_reparent");
 }

@@ -273,7 +273,7 @@ extern "C" int lav_swin_block_bwd(void* stream, void* side_stream, const lav_swi
 
 // One fusion layer over the new rows of a decoding step (model_for_captioning.py:96-130 with a key / value cache): the arithmetic of
 // lav_bert_layer_fwd at eval, on skinny GEMMs and the decode attention.
-extern "C" int lav_bert_layer_decode(void* stream, const lav_bert_layer_decode_desc* d) {
+static int bert_layer_decode(void* stream, const lav_bert_layer_decode_desc* d, int beams) {
     LAV_REQUIRE(d, "lav_bert_layer_decode: null descriptor");
     LAV_REQUIRE(d->B > 0 && d->q_len > 0 && d->B * d->q_len <= 64 && d->hidden > 0 && d->heads > 0 && d->hidden == 64 * d->heads && d->ffn > 0,
                 "lav_bert_layer_decode: B=%d q_len=%d (B * q_len <= 64) hidden=%d heads=%d ffn=%d", d->B, d->q_len, d->hidden, d->heads, d->ffn);
@@ -289,7 +289,7 @@ extern "C" int lav_bert_layer_decode(void* stream, const lav_bert_layer_decode_d
         a.prefix_qkv = d->prefix_qkv; a.ld_prefix = 3 * H; a.key_mask = d->key_mask;
         a.qkv_new = d->qkv; a.ld_new = 3 * H; a.cache_k = d->cache_k; a.cache_v = d->cache_v; a.out = d->cx; a.ldo = H;
         a.partials = d->attn_partials; a.partials_capacity = d->attn_partials_capacity;
-        LAV_TRY(lav_attention_decode(stream, &a));
+        LAV_TRY(beams == 1 ? lav_attention_decode(stream, &a) : lav_attention_decode_beam(stream, &a, beams));
     }
     LAV_TRY(lav_gemm_skinny_bf16(stream, R, H, H, d->cx, H, d->w_ao, H, d->b_ao, LAV_SKINNY_RES_F32, d->x_res, H, d->x_res_bf16, d->pre1, H));
     lav_ln_f32 f32io; f32io.x_f32 = 1; f32io.y32 = d->x1_32; f32io.ldy32 = H;
@@ -300,4 +300,13 @@ extern "C" int lav_bert_layer_decode(void* stream, const lav_bert_layer_decode_d
     LAV_TRY(lav_layernorm_fwd(stream, R, H, d->pre2, H, nullptr, d->ln2_gamma, d->ln2_beta, d->ln2_eps > 0.f ? d->ln2_eps : d->ln_eps, d->y, H,
                               d->ln_stats, d->ln_stats + R, &f32o));
     return LAV_OK;
+}
+
+extern "C" int lav_bert_layer_decode(void* stream, const lav_bert_layer_decode_desc* d) { return bert_layer_decode(stream, d, 1); }
+
+// the same over clips * beams row groups whose video keys are their clip's (lav_attention_decode_beam)
+extern "C" int lav_bert_layer_decode_beam(void* stream, const lav_bert_layer_decode_desc* d, int beams) {
+    LAV_REQUIRE(d && beams >= 1 && beams <= LAV_BEAM_MAX && d->B % beams == 0, "lav_bert_layer_decode_beam: beams=%d (1..%d) must divide B=%d",
+                beams, LAV_BEAM_MAX, d ? d->B : 0);
+    return bert_layer_decode(stream, d, beams);
 }

@@ -692,3 +692,53 @@ def greedy_step(logits, V, ids, cur, penalty, unfinished, score_sum, count, pad_
 
 def bert_layer_decode(desc):
     L.check(L.lib.lav_bert_layer_decode(_s(), C.byref(desc)), "lav_bert_layer_decode")
+
+
+# ---- beam search (csrc/decode.hip) ----------------------------------------------------------------------------------------------
+BEAM_MAX = 8                                 # LAV_BEAM_MAX
+
+
+def attention_decode_beam(desc, beams):
+    L.check(L.lib.lav_attention_decode_beam(_s(), C.byref(desc), int(beams)), "lav_attention_decode_beam")
+
+
+def bert_layer_decode_beam(desc, beams):
+    L.check(L.lib.lav_bert_layer_decode_beam(_s(), C.byref(desc), int(beams)), "lav_bert_layer_decode_beam")
+
+
+def beam_step(logits, V, ids, cur, penalty, beam_scores, beams, cand_score, cand_word):
+    """per row: penalty in place, top 2 * beams of log_softmax + beam score -> cand_score / cand_word (rows, 2 * beams): lav_beam_step"""
+    rows = logits.shape[0]
+    L.check(L.lib.lav_beam_step(_s(), rows, int(beams), V, _p(logits), logits.stride(0), _p(ids), ids.stride(0), cur, float(penalty), _p(beam_scores),
+                                _p(cand_score), _p(cand_word)), "lav_beam_step")
+
+
+def beam_select_desc(clips, beams, keep, V, max_len, early_stopping, eos_id, pad_id, cand_score, cand_word, beam_scores, ids, parent, hyp_ids,
+                     hyp_score, hyp_seq, state, worst, next_ids=None, ld_next=0):
+    """the descriptor of lav_beam_select; cur, cur_norm and max_norm are set per step (beam_select)"""
+    return L.BeamSelectDesc(clips, beams, keep, V, 0, max_len, int(bool(early_stopping)), 1.0, 1.0, int(eos_id), int(pad_id), _dp(cand_score),
+                            _dp(cand_word), _dp(beam_scores), _dp(ids), ids.stride(0), _dp(next_ids), ld_next, _dp(parent), _dp(hyp_ids),
+                            _dp(hyp_score), _dp(hyp_seq), _dp(state), _dp(worst))
+
+
+def beam_select(desc, cur, cur_norm, max_norm):
+    desc.cur, desc.cur_norm, desc.max_norm = cur, cur_norm, max_norm
+    L.check(L.lib.lav_beam_select(_s(), C.byref(desc)), "lav_beam_select")
+
+
+def beam_reparent_desc(src, dst, parent, max_len):
+    """src / dst: lists of per-layer (k, v) caches (rows, heads, max_len, 64) bf16"""
+    n = len(src)
+    if n > L.REPARENT_MAX_LAYERS:
+        raise ValueError(f"lav_beam_reparent: {n} layers, at most {L.REPARENT_MAX_LAYERS}")
+    rows, heads = src[0][0].shape[:2]
+    d = L.BeamReparentDesc(n, rows, heads, 0, max_len, _dp(parent))
+    for i in range(n):
+        d.src_k[i], d.src_v[i] = src[i][0].data_ptr(), src[i][1].data_ptr()
+        d.dst_k[i], d.dst_v[i] = dst[i][0].data_ptr(), dst[i][1].data_ptr()
+    return d
+
+
+def beam_reparent(desc, n_pos):
+    desc.n_pos = n_pos
+    L.check(L.lib.lav_beam_reparent(_s(), C.byref(desc)), "lav_beam_reparent")
