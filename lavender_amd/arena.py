@@ -262,9 +262,12 @@ class ParamArena:
         dw_join()
         if self.ft_units:
             K.zero_blocks(self.grad_full, self._zero_blocks, ALIGN)      # vectors and tables (atomic accumulation); the matrices are assigned by their first writer
+            # a listener (the data-parallel reducer) may have written into a CLEAN unit after finish_first_touch zeroed it -- an all-reduce
+            # lands the other ranks' gradient there -- so with listeners attached every unit is re-armed, whoever wrote its memory
+            rearm_all = bool(self.listeners)
             n = 0
             for u in self.ft_units:
-                if u.state:                                   # WRITTEN (or still ARMED): the memory is stale from here on
+                if u.state or rearm_all:                      # WRITTEN (or still ARMED, or possibly written by a listener): stale from here on
                     u.state = 1
                     n += 1
             self._ft_armed = n

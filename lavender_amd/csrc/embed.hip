@@ -414,6 +414,8 @@ extern "C" int lav_gather_sum_rows(void* stream, int n_out, int C, const void* s
 }
 
 // ---- key mask of a pair list: out[k][c] = c < Lv ? mask_img[vi[k]][c] : mask_txt[ti[k]][c - Lv]  (int32, what the sequence-attention kernels read) ----
+// vi / ti are NOT bounds-checked here: the caller validates them against B and nt (lavender_amd/hip.py pair_key_mask).  A mask with no columns is
+// never read and may be null (torch hands out a null pointer for an empty tensor).
 __global__ __launch_bounds__(256) void pair_key_mask_kernel(int n, int Lv, int X, const int64_t* __restrict__ mimg, const int64_t* __restrict__ mtxt,
                                                            const int32_t* __restrict__ vi, const int32_t* __restrict__ ti, int32_t* __restrict__ out) {
     const int L = Lv + X;
@@ -426,7 +428,7 @@ __global__ __launch_bounds__(256) void pair_key_mask_kernel(int n, int Lv, int X
 
 extern "C" int lav_pair_key_mask(void* stream, int n, int Lv, int X, const int64_t* mask_img, const int64_t* mask_txt, const int32_t* vi,
                                  const int32_t* ti, int32_t* out) {
-    LAV_REQUIRE(n > 0 && Lv >= 0 && X >= 0 && Lv + X > 0 && mask_img && mask_txt && vi && ti && out, "lav_pair_key_mask: bad arguments n=%d Lv=%d X=%d", n, Lv, X);
+    LAV_REQUIRE(n > 0 && Lv >= 0 && X >= 0 && Lv + X > 0 && (Lv == 0 || mask_img) && (X == 0 || mask_txt) && vi && ti && out, "lav_pair_key_mask: bad arguments n=%d Lv=%d X=%d", n, Lv, X);
     const long tot = (long)n * (Lv + X);
     hipLaunchKernelGGL(pair_key_mask_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, Lv, X, mask_img, mask_txt, vi, ti, out);
     return lav_check_launch("lav_pair_key_mask");

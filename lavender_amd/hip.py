@@ -529,9 +529,31 @@ def text_embed_bwd(ids, dout, n, X, Hd, word, pos, type0, gamma, mean, rstd, dro
                                      _p(d_type0), _p(dgamma), _p(dbeta)), "lav_text_embed_bwd")
 
 
-def pair_key_mask(mask_img, mask_txt, vi32, ti32):
-    """(n, Lv + X) int32 key mask of the pair list (vi32[k], ti32[k]) from the int64 (B, Lv) / (nt, X) masks: lav_pair_key_mask."""
-    n, Lv, X = vi32.shape[0], mask_img.shape[1], mask_txt.shape[1]
+def _pair_index(idx, bound, what, device):
+    """int32 device copy of a pair-list index, every entry checked against [0, bound) on the host first: the kernel reads the mask rows it names
+    without a bounds check.  Host arrays (what the model passes) cost no device read; a device tensor is read back once."""
+    if isinstance(idx, torch.Tensor):
+        host = idx.detach().to("cpu", torch.int64)
+    else:
+        import numpy as np
+        host = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))
+    host = host.reshape(-1)
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= bound):
+        raise ValueError(f"pair_key_mask: {what} holds {int(host.min())}..{int(host.max())}, outside [0, {bound})")
+    if isinstance(idx, torch.Tensor) and idx.device == device and idx.dtype == torch.int32 and idx.is_contiguous():
+        return idx
+    # non-blocking upload: a synchronous copy would wait for everything queued so far
+    return host.to(torch.int32).to(device, non_blocking=True)
+
+
+def pair_key_mask(mask_img, mask_txt, vi, ti):
+    """(n, Lv + X) int32 key mask of the pair list (vi[k], ti[k]) from the int64 (B, Lv) / (nt, X) masks: lav_pair_key_mask.
+    vi / ti: host arrays or device tensors; an index outside [0, B) / [0, nt) raises ValueError before anything is launched."""
+    n, Lv, X = len(vi), mask_img.shape[1], mask_txt.shape[1]
+    if len(ti) != n:
+        raise ValueError(f"pair_key_mask: {n} video indices but {len(ti)} text indices")
+    vi32 = _pair_index(vi, mask_img.shape[0], "vi", mask_img.device)
+    ti32 = _pair_index(ti, mask_txt.shape[0], "ti", mask_img.device)
     if mask_img.dtype != torch.int64 or not mask_img.is_contiguous():
         mask_img = mask_img.long().contiguous()
     if mask_txt.dtype != torch.int64 or not mask_txt.is_contiguous():

@@ -262,11 +262,9 @@ class LAVENDER_Base(nn.Module):
         """go_cross on the pair list (video vi[k], text ti[k]) without materialising per-pair copies in Python
         (replaces the list building + T.cat of main_pretrain_mlm.py:74-111)."""
         feat, pair = self._pair_source(feat_img, feat_txt, vi, ti)
-        # non-blocking uploads: torch.as_tensor(..., device=) is a synchronous copy that waits for everything queued so far (it cost
-        # two device drains per step, 2 x 18 ms of host stall at the cfg2 shape)
-        vi_t = torch.from_numpy(np.ascontiguousarray(vi, dtype=np.int32)).to(mask_img.device, non_blocking=True)
-        ti_t = torch.from_numpy(np.ascontiguousarray(ti, dtype=np.int32)).to(mask_img.device, non_blocking=True)
-        mask = K.pair_key_mask(mask_img, mask_txt, vi_t, ti_t)     # (n, L) int32: get_attn_mask("full") over the pair list, one launch
+        # host index arrays: checked against B / nt on the host and uploaded without blocking (torch.as_tensor(..., device=) is a synchronous
+        # copy that waits for everything queued so far: it cost two device drains per step, 2 x 18 ms of host stall at the cfg2 shape)
+        mask = K.pair_key_mask(mask_img, mask_txt, vi, ti)         # (n, L) int32: get_attn_mask("full") over the pair list, one launch
         return self._encode(feat, mask, pair=pair), _NO_ATTN
 
     def prepro_txt_inputs(self, txt, mask_txt, feat_txt, task_name=None, prompt=None):

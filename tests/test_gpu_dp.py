@@ -249,3 +249,137 @@ def test_zero1_and_bf16_buckets_over_rccl_single_rank(zero, bf16):
                 pytest.fail(f"RCCL worker failed (exit code {p.exitcode})")
     p.join(timeout=60)
     assert res is True
+
+
+# ---- first-touch units when the ranks write different matrices -----------------------------------------------------------------------------------
+def _pair_backward(agent, m, rank, with_vtm):
+    """one backward of LAVENDER_Pretrain on `rank`'s batch: the MTM loss, plus the VTM loss (the only one through the score head `fc`) when asked"""
+    from tests.helpers import BERT_CFGS, make_batch
+    b = make_batch(2, vocab=BERT_CFGS["micro"]["vocab"], seed=30 + rank)
+    torch.manual_seed(50 + rank)
+    b.update(agent.masking(b["txt"], b["mask"]))
+    batch = agent.prepare_batch(b)
+    m.eval()                                            # deterministic (no dropout) so ranks can be replayed
+    m.arena().zero_grad()
+    np.random.seed(rank)
+    out = agent.forward_step((batch["img"], batch["txt"], batch["mask"], batch["ans_mtm"]))
+    ls = agent.loss_func(out["out_mtm"].flatten(0, 1), out["ans_mtm"].flatten())
+    if with_vtm:
+        ls = ls + agent.loss_func(out["out_vtm"], out["ans_vtm"], out["ans_vtm"].shape[0])
+    ls.backward()
+    from lavender_amd.engine import dw_join
+    dw_join()
+
+
+def _fresh_pair_grads(agent, m, rank, with_vtm):
+    """rank's gradient of this step computed alone: reducer detached, arena zeroed; the arena's memory and first-touch states are put back after,
+    so the data-parallel step that follows starts from exactly what the previous one left"""
+    a = m.arena()
+    saved, states, armed = a.grad_full.clone(), [u.state for u in a.ft_units], a._ft_armed
+    listeners, a.listeners = a.listeners, []
+    a.grad_full.zero_()
+    for u in a.ft_units:
+        u.state = 0
+    a._ft_armed = 0
+    _pair_backward(agent, m, rank, with_vtm)
+    g = a.grad.clone()
+    a.grad_full.copy_(saved)
+    for u, s in zip(a.ft_units, states):
+        u.state = s
+    a._ft_armed, a.listeners = armed, listeners
+    return g
+
+
+FT_PLAN = [(True, False), (False, False), (True, True)]          # (rank 0 backpropagates VTM, rank 1 backpropagates VTM) per step
+
+
+def _first_touch_worker(rank, world, port, q, zero):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0")
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    import lavender_amd as LA
+    from tests.helpers import Tok, make_args
+    torch.manual_seed(200 + rank)
+    args = make_args("micro", "micro", 2, lr=1e-3, deepspeed=zero)
+    m = LA.LAVENDER_Pretrain(args, Tok()).cuda()
+    a = m.arena()
+    agent = LA.Agent_Pretrain(args, m)
+    agent.prepare_dist_model()
+    assert agent.dp.world == world and agent.dp.zero_stage == (1 if zero else 0)
+    u = m.fc[1].weight.__dict__.get("_lav_ft")
+    assert u is not None and m.fc[1].weight.numel() == 256 * 128, "fc.1.weight must be a first-touch unit"
+    lo, hi = (agent.dp.lo, agent.dp.hi) if zero else (0, a.total)          # ZeRO-1: only the own shard holds the sum
+    flo, fhi = max(u.lo, lo), min(u.hi, hi)                              # the part of fc this rank checks
+    res = []
+    for step, plan in enumerate(FT_PLAN):
+        fresh = [_fresh_pair_grads(agent, m, r, plan[r]) for r in range(world)]
+        ref = fresh[0] + fresh[1]
+        agent.dp.begin_step()
+        _pair_backward(agent, m, rank, plan[rank])
+        agent.dp.finish()
+        torch.cuda.synchronize()
+        g = a.grad.clone()
+        rel = float((g[lo:hi] - ref[lo:hi]).double().norm() / ref[lo:hi].double().norm())
+        fc_err = float((g[flo:fhi] - ref[flo:fhi]).abs().max()) if fhi > flo else 0.0
+        fc_max = float(g[flo:fhi].abs().max()) if fhi > flo else 0.0
+        fc_ref = float(ref[flo:fhi].abs().max()) if fhi > flo else 0.0
+        same_grad = True
+        if not zero:                                                     # replicated mode: both ranks hold the same sum
+            g0 = g.clone()
+            dist.broadcast(g0, src=0)
+            same_grad = bool(torch.equal(g0, g))
+        agent.optzr.step(max_norm=1.0, dp=agent.dp)
+        agent.dp.gather_master()
+        torch.cuda.synchronize()
+        w0 = a.master.clone()
+        dist.broadcast(w0, src=0)
+        res.append(dict(step=step + 1, rel=rel, fc_err=fc_err, fc_max=fc_max, fc_ref=fc_ref, fc_elems=max(0, fhi - flo), same_grad=same_grad,
+                        same_master=bool(torch.equal(w0, a.master))))
+    q.put((rank, res))
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("zero", [False, True])
+def test_first_touch_unit_written_by_one_rank_only(zero):
+    """Ranks that differ in which matrices they write (arena.py first-touch + dp.py).  Step 1: rank 0 backpropagates MTM + VTM (the
+    VTM loss goes through the score head fc), rank 1 MTM only -- on rank 1 fc is zeroed, then the all-reduce leaves rank 0's gradient in it.
+    Step 2: both MTM only -- nobody writes fc, so its reduced gradient must be exactly zero, not the previous sum carried over.  Step 3: both
+    MTM + VTM.  After every finish() the (own shard of the) arena equals the sum of the ranks' fresh gradients and the replicas stay
+    bit-identical through the optimizer steps.  Break caught: zero_grad leaving a CLEAN unit that a reducer wrote into un-armed."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = 30000 + (os.getpid() % 1000) + (19 if zero else 0)
+    ps = [ctx.Process(target=_first_touch_worker, args=(r, 2, port, q, zero)) for r in range(2)]
+    for p in ps:
+        p.start()
+    import queue as _queue
+    import time as _time
+    res, t0 = [], _time.time()
+    while len(res) < len(ps):                                    # fail fast when a rank dies instead of waiting out the timeout
+        try:
+            res.append(q.get(timeout=2))
+        except _queue.Empty:
+            dead = [p.exitcode for p in ps if p.exitcode not in (None, 0)]
+            if dead or _time.time() - t0 > 300:
+                for p in ps:
+                    if p.is_alive():
+                        p.terminate()
+                pytest.fail(f"data-parallel worker failed (exit codes {[p.exitcode for p in ps]})")
+    for p in ps:
+        p.join(timeout=60)
+    res = dict(res)
+    for rank in (0, 1):
+        for r in res[rank]:
+            print(f"zero={zero} rank {rank} step {r['step']}: rel {r['rel']:.3e}, fc max|g| {r['fc_max']:.4g} (fresh sum {r['fc_ref']:.4g}, "
+                  f"max|d| {r['fc_err']:.3g}), grads equal {r['same_grad']}, masters equal {r['same_master']}")
+    assert res[0][0]["fc_elems"] + res[1][0]["fc_elems"] > 0
+    for rank in (0, 1):
+        for r in res[rank]:
+            what = f"rank {rank}, step {r['step']}"
+            # the gradient sum is order-dependent only through the float atomics of the vector gradients
+            assert r["rel"] < 1e-4, (what, r)
+            assert r["fc_err"] <= 1e-5 * max(r["fc_ref"], 1e-30) + 1e-30, (what, r)
+            assert r["same_grad"] and r["same_master"], (what, r)
+        assert res[rank][1]["fc_max"] == 0.0, f"rank {rank}: fc holds {res[rank][1]['fc_max']} after a step in which no rank wrote it"
+        assert res[rank][0]["fc_elems"] == 0 or res[rank][0]["fc_ref"] > 0

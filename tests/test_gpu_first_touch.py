@@ -179,3 +179,66 @@ def test_a_weight_nobody_writes_reads_as_zero_not_as_last_steps_gradient():
     assert u.state == 1
     E.G(next(p for p in m1.parameters() if p.__dict__.get("_lav_ft") is u))
     assert u.state == 2 and float(ar.grad[u.lo:u.hi].abs().max()) == 0.0
+
+
+def test_a_listener_write_into_a_clean_unit_is_not_read_as_next_steps_gradient():
+    """The contract the data-parallel reducer relies on: a listener of the arena (dp.ArenaReducer) may write into a unit after finish_first_touch
+    has zeroed it and marked it CLEAN (its all-reduce lands the other ranks' gradient there).  The next step must still read zero where nobody
+    writes.  A stub listener plays the reducer on the score head `fc` of LAVENDER_Pretrain, which only the VTM loss writes.  Break caught: zero_grad
+    re-arming only the units with a non-zero state."""
+    import lavender_amd as LA
+    from lavender_amd.engine import dw_join
+    args = make_args("micro", "micro", 2, lr=1e-3)
+    torch.manual_seed(3)
+    m = LA.LAVENDER_Pretrain(args, Tok()).cuda()
+    ar = m.arena()
+    ag = LA.Agent_Pretrain(args, m)
+    u = m.fc[1].weight.__dict__.get("_lav_ft")
+    assert u is not None
+
+    def backward(with_vtm):
+        b = make_batch(2, vocab=BERT_CFGS["micro"]["vocab"], seed=30)
+        torch.manual_seed(50)
+        b.update(ag.masking(b["txt"], b["mask"]))
+        batch = ag.prepare_batch(b)
+        m.eval()
+        ar.zero_grad()
+        np.random.seed(0)
+        out = ag.forward_step((batch["img"], batch["txt"], batch["mask"], batch["ans_mtm"]))
+        ls = ag.loss_func(out["out_mtm"].flatten(0, 1), out["ans_mtm"].flatten())
+        if with_vtm:
+            ls = ls + ag.loss_func(out["out_vtm"], out["ans_vtm"], out["ans_vtm"].shape[0])
+        ls.backward()
+        dw_join()
+        torch.cuda.synchronize()
+        return ar.grad[u.lo:u.hi].clone()
+
+    g_fc = backward(True)                                          # no listener yet: the plain gradient of fc
+    assert float(g_fc.abs().max()) > 0
+
+    class Stub:
+        writes = 0
+        events = 0
+
+        def __call__(self, event):
+            if event != "fusion_grads_final":
+                return
+            self.events += 1
+            ar.finish_first_touch(u.lo, u.hi)                       # what ArenaReducer._reduce does first
+            if self.writes:
+                ar.grad[u.lo:u.hi].fill_(3.0)                      # ... and what its all-reduce leaves there: another rank's gradient
+                self.writes -= 1
+
+    stub = Stub()
+    ar.listeners.append(stub)
+    try:
+        backward(True)
+        stub.writes = 1
+        g = backward(False)                                        # fc not written here: zeroed, CLEAN, then written by the listener
+        assert stub.events == 2 and u.state == 0 and bool((g == 3.0).all())
+        g = backward(False)                                        # nobody writes fc in this step: it must read zero
+        assert float(g.abs().max()) == 0.0, f"fc holds {float(g.abs().max())}: the listener's write was carried into the next step"
+        g = backward(True)                                         # written again: the plain gradient, nothing added to it
+        assert torch.allclose(g, g_fc, rtol=1e-5, atol=0)
+    finally:
+        ar.listeners.remove(stub)
