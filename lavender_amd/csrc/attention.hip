@@ -793,9 +793,10 @@ extern "C" int lav_attention_bwd(void* stream, const lav_attn_desc* d, const voi
     return lav_check_launch("lav_attention_bwd");
 }
 
-// Bias-table gradient alone (window mode; persistent N <= 256 path or large-window path): needs the forward's lse and the -delta scratch that
-// lav_attention_bwd (called first, with dbias_table = NULL) left behind the lse in the same buffer.  A parameter gradient:
-// the engine issues it on the weight-gradient stream.
+// Bias-table gradient alone (window mode; persistent N <= 256 path or large-window path): needs the forward's lse and the delta scratch that
+// lav_attention_bwd (called first, with dbias_table = NULL) left behind the lse in the same buffer -- stored NEGATED by the persistent
+// kernels (win_dq3 / win_bwd1: -delta is the C operand of their dP MFMAs), as +delta by the large-window ones (winl_dq).  A parameter
+// gradient: the engine issues it on the weight-gradient stream.
 extern "C" int lav_attention_bwd_bias(void* stream, const lav_attn_desc* d, const void* qkv, const void* dout, const float* lse,
                                       float* dbias_table) {
     AttnArgs a; int problems = 0;
