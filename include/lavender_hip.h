@@ -50,7 +50,7 @@ const char* lav_last_error(void);
 #define LAV_WS_LN_DEFER 2
 size_t lav_workspace_bytes(int kind);
 int lav_set_workspace(void* stream, int kind, void* ptr, size_t bytes);
-int lav_abi_version(void);   /* 7: lav_bert_layer_desc.ln2_eps, lav_pair_key_mask, lav_gemm_epilogue.assign / lav_gemm_tn_job.assign / lav_*_bwd_desc.assign_mask (first-touch weight gradients), lav_winl_select declared, lav_set_error no longer exported; 6: lav_workspace_bytes / lav_set_workspace, lav_layernorm_set_defer per stream + lav_layernorm_flush_all, lav_ln_bwd_extra.finish_stream removed, LAV_E_WORKSPACE; 5: lav_gemm_tn_grouped (+ lav_*_bwd_desc.group_splits), fp16 rows (out_mode 3, residual_f32 / x_f32 = 2, lav_bert_layer_desc.stream_f16), lav_layernorm_set_defer / lav_layernorm_flush, lav_attn_desc.bias_map / lav_attention_build_bias_map; 4: lav_gemm_epilogue.c_pad_writable; 3: a_rowmap / res_rowmap / res_ln_*; 2: residual_f32, lav_ln_f32, causal_from, lav_scale_by_scalar, lav_v_* validation entries, lavender_pipeline.h */
+int lav_abi_version(void);   /* 7: lav_text_embed_pre_fwd / lav_text_embed_pre_bwd (additive), lav_bert_layer_desc.ln2_eps, lav_pair_key_mask, lav_gemm_epilogue.assign / lav_gemm_tn_job.assign / lav_*_bwd_desc.assign_mask (first-touch weight gradients), lav_winl_select declared, lav_set_error no longer exported; 6: lav_workspace_bytes / lav_set_workspace, lav_layernorm_set_defer per stream + lav_layernorm_flush_all, lav_ln_bwd_extra.finish_stream removed, LAV_E_WORKSPACE; 5: lav_gemm_tn_grouped (+ lav_*_bwd_desc.group_splits), fp16 rows (out_mode 3, residual_f32 / x_f32 = 2, lav_bert_layer_desc.stream_f16), lav_layernorm_set_defer / lav_layernorm_flush, lav_attn_desc.bias_map / lav_attention_build_bias_map; 4: lav_gemm_epilogue.c_pad_writable; 3: a_rowmap / res_rowmap / res_ln_*; 2: residual_f32, lav_ln_f32, causal_from, lav_scale_by_scalar, lav_v_* validation entries, lavender_pipeline.h */
 
 /* ---------------------------------------------------------------------------------------------
  * GEMM with fused epilogue.  Replaces every nn.Linear on the path (video_swin.py:73-79,137-139,
@@ -321,6 +321,24 @@ int lav_text_embed_bwd(void* stream, int n, int X, int Hd, const int64_t* ids, c
                        const float* pos, const float* type0, const float* gamma, const float* mean, const float* rstd,
                        float dropout_p, uint32_t seed, float* d_word, float* d_pos, float* d_type0, float* dgamma,
                        float* dbeta);
+
+/* (ABI 7, additive) Text embedding behind a pre-text segment (LAVENDER_Base.get_pretxt / prepro_txt_inputs, model.py:250-307: a task token
+ * emb_task[task_tok2id[task]] or an embedded prompt between the video rows and the text rows).  Text j's block of `out` is Lp + X rows
+ * [pre-text ; text]: the Lp pre-text rows are copied from the bf16 rows pre + j * pre_stride (pre_stride 0: ONE (Lp, Hd) block for every
+ * text; Lp * Hd: a block per text), the X text rows are those of lav_text_embed_fwd bit for bit (same dropout keys; mean / rstd (n * X)
+ * indexed as there).  Lp = 0 is lav_text_embed_fwd.  pre: 16-byte aligned. */
+int lav_text_embed_pre_fwd(void* stream, int n, int Lp, int X, int Hd, const int64_t* ids, const float* word, const float* pos,
+                           const float* type0, const float* gamma, const float* beta, float eps, float dropout_p, uint32_t seed,
+                           const void* pre, long pre_stride, void* out, float* mean, float* rstd);
+/* Backward of lav_text_embed_pre_fwd over the (n, Lp + X, Hd) dout: the parameter gradients of lav_text_embed_bwd from the text rows, and
+ * the pre-text gradient.  pre_stride 0: d_pre = sum_j dout[j, 0:Lp], summed in fp32 in a fixed order (run-to-run identical, no float
+ * atomics; n >= 8 texts are split over workgroups whose fp32 partials go to the stream's LAV_WS_LN_PARTIALS workspace, groups * Lp * Hd * 4
+ * bytes, and a second launch sums them in group order); d_pre_mode 0 accumulates that sum into the fp32 (Lp, Hd) d_pre (a parameter-gradient
+ * row), 1 writes it as bf16 rows.  pre_stride Lp * Hd: d_pre_mode must be 1 and d_pre (n, Lp, Hd) bf16 receives each text's own rows. */
+int lav_text_embed_pre_bwd(void* stream, int n, int Lp, int X, int Hd, const int64_t* ids, const void* dout, const float* word,
+                           const float* pos, const float* type0, const float* gamma, const float* mean, const float* rstd,
+                           float dropout_p, uint32_t seed, float* d_word, float* d_pos, float* d_type0, float* dgamma,
+                           float* dbeta, long pre_stride, void* d_pre, int d_pre_mode);
 
 /* Row gather / gather-sum: builds the fusion input [video rows of sample vi | text rows of sample ti]
  * (go_cross concat model.py:235 + VTM pairing main_pretrain_mlm.py:74-111) and its backward. */

@@ -161,6 +161,8 @@ _SIGS = {
     "lav_video_embed_bwd": (i32, [vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lav_text_embed_fwd": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, u32, vp, vp, vp]),
     "lav_text_embed_bwd": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, u32, vp, vp, vp, vp, vp]),
+    "lav_text_embed_pre_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, u32, vp, i64, vp, vp, vp]),
+    "lav_text_embed_pre_bwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, u32, vp, vp, vp, vp, vp, i64, vp, i32]),
     "lav_gather_rows": (i32, [vp, i32, i32, vp, i64, vp, vp, i64]),
     "lav_gather_sum_rows": (i32, [vp, i32, i32, vp, i64, vp, vp, vp, i64]),
     "lav_pair_key_mask": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),

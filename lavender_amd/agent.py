@@ -75,6 +75,16 @@ class ArenaAdamW:
         self.model.arena().zero_grad()
 
 
+def set_pretxt(args, batch, dl, task_name):
+    """the pre-text switches of the reference's go_dl loops (e.g. main_qaoe_mlm.py:108-111): the dataset's prompt under args.enable_prompt,
+    else the task name under args.enable_task_token"""
+    if getattr(args, "enable_prompt", False):
+        batch["prompt"] = dl.dataset.get_prompt()
+    elif getattr(args, "enable_task_token", False):
+        batch["task_name"] = task_name
+    return batch
+
+
 class CrossEntropyIgnore:
     """T.nn.CrossEntropyLoss(ignore_index=-1) of agent.py:72 on the HIP engine.  `count` (number of labelled
     rows) may be given when the host already knows it (labels are built on the host)."""

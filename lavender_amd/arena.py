@@ -56,6 +56,15 @@ SLACK = 64 * 1024
 # parameters that never receive a gradient on the paths built here (after one pretrain step exactly these
 # have grad None in the reference, so torch.optim.AdamW never touches them -- no weight decay either); bit 2 of block_group
 NO_GRAD_PARAMS = ("emb_task", "enc_img.emb_odr")
+
+
+def no_grad_params(module):
+    """NO_GRAD_PARAMS of this model: with args.enable_task_token the task-token table is read by every task-token pass and is an ordinary
+    parameter (AdamW updates and decays all its rows, group "other/decay", as torch.optim.AdamW does in the reference)"""
+    args = getattr(module, "args", None)
+    if getattr(args, "enable_task_token", False):
+        return tuple(n for n in NO_GRAD_PARAMS if n != "emb_task")
+    return NO_GRAD_PARAMS
 _QKV = re.compile(r"(.*attention\.self)\.(query|key|value)\.(weight|bias)$")
 
 
@@ -109,6 +118,7 @@ class ParamArena:
         self.grad_full = torch.zeros(off + SLACK, dtype=torch.float32, device=self.device)
         self.grad = self.grad_full[:off]
         grp = torch.zeros(off // ALIGN, dtype=torch.uint8)
+        no_grad = no_grad_params(module)
         self.params = {}
         for n, p in named:
             o, k = self.offsets[n], p.numel()
@@ -118,7 +128,7 @@ class ParamArena:
             p._lav16 = self.half[o:o + k].view(p.shape)
             p._lavg = p.grad
             p._lav_name = n
-            grp[o // ALIGN:(o + k + ALIGN - 1) // ALIGN] = param_group_of(n) | (4 if n in NO_GRAD_PARAMS else 0)
+            grp[o // ALIGN:(o + k + ALIGN - 1) // ALIGN] = param_group_of(n) | (4 if n in no_grad else 0)
             self.params[n] = p
         self.block_group = grp.to(self.device)
         self._build_transposed(named)

@@ -251,6 +251,26 @@ class KVDecoder:
             d.cache_k, d.cache_v = k.data_ptr(), v.data_ptr()
 
 
+def encode_prefix(model, img, pretxt=None):
+    """the fully visible prefix of every clip: its video rows, then the pre-text (model_for_captioning.py:160-176, 258-290: the task token or the
+    embedded prompt sits between the video and the caption, whose positions still count from 0) -- (feat (B, Lv + Lp, H), key mask (B, Lv + Lp)).
+    The prefix's rows see only prefix keys, so the cached path runs it once per clip like the video rows alone (Lv' = Lv + Lp) and the literal
+    path masks with causal_from = Lv + Lp.  pretxt: LAVENDER_Base._pretxt_spec("cap", prompt), or None."""
+    feat_img, mask_img = model.enc_img(img)
+    if pretxt is None:
+        return feat_img, mask_img
+    B, H = feat_img.shape[0], feat_img.shape[2]
+    if pretxt[0] == "task":
+        pf = E.W16(model.emb_task)[pretxt[1]].view(1, 1, H)
+    else:
+        pf = model._embed_prompt(pretxt[1][0], feat_img.device)
+    pf = pf.expand(B, -1, -1) if pf.shape[0] == 1 else pf
+    assert pf.shape[0] == B, f"a per-clip prompt needs one row block per clip ({pf.shape[0]} for {B} clips)"
+    feat = torch.cat([feat_img, pf.to(feat_img.dtype)], 1)
+    mask = torch.cat([mask_img, torch.ones((B, pf.shape[1]), dtype=mask_img.dtype, device=mask_img.device)], 1)
+    return feat, mask
+
+
 def recompute_logits(model, feat_img, mask_img, ids, cur_len):
     """the reference's step (model_for_captioning.py:96-130, past is None): text [ids[:, :cur_len] ; MASK] at positions 0..cur_len, the whole
     fusion encoder over Lv + cur_len + 1 rows under the seq2seq mask, the MLM head at the [MASK] row; fp32 (B, V)"""
@@ -265,19 +285,19 @@ def recompute_logits(model, feat_img, mask_img, ids, cur_len):
 KV_MAX_CLIPS = 32          # the cached path decodes at most this many clips at once: 2 rows per clip through the skinny GEMMs (M <= 64)
 
 
-def generate(model, img, X, cfg, kv=None, generator=None, forced_ids=None, step_logits=None):
+def generate(model, img, X, cfg, kv=None, generator=None, forced_ids=None, step_logits=None, pretxt=None):
     """(ids (B, 1, max_len), logprob (B, 1)).  forced_ids (B, max_len): teacher forcing (tests; the chosen tokens are replaced by these
     before the next step); step_logits: a list that receives each step's fp32 [MASK] logits (B, V) before the penalty.  The cached path
     decodes larger batches in chunks of KV_MAX_CLIPS clips (every clip's caption is independent of the others)."""
     kv = KV if kv is None else kv
     B = img.shape[0]
     if not kv or B <= KV_MAX_CLIPS:
-        return _generate(model, img, X, cfg, kv, generator, forced_ids, step_logits)
+        return _generate(model, img, X, cfg, kv, generator, forced_ids, step_logits, pretxt)
     ids, lps, chunk_steps = [], [], []
     for s in range(0, B, KV_MAX_CLIPS):
         st = [] if step_logits is not None else None
         i, lp = _generate(model, img[s:s + KV_MAX_CLIPS], X, cfg, kv, generator,
-                          None if forced_ids is None else forced_ids[s:s + KV_MAX_CLIPS], st)
+                          None if forced_ids is None else forced_ids[s:s + KV_MAX_CLIPS], st, pretxt)
         ids.append(i)
         lps.append(lp)
         chunk_steps.append(st)
@@ -286,9 +306,9 @@ def generate(model, img, X, cfg, kv=None, generator=None, forced_ids=None, step_
     return torch.cat(ids, 0), torch.cat(lps, 0)
 
 
-def _generate(model, img, X, cfg, kv, generator, forced_ids, step_logits):
+def _generate(model, img, X, cfg, kv, generator, forced_ids, step_logits, pretxt=None):
     pad_id, eos_id, cls_id = model.pad_token_id, model.sep_token_id, model.cls_token_id
-    feat_img, mask_img = model.enc_img(img)
+    feat_img, mask_img = encode_prefix(model, img, pretxt)
     B, dev, L = feat_img.shape[0], feat_img.device, cfg.max_len
     ids = torch.full((B, L), pad_id, dtype=torch.long, device=dev)
     ids[:, 0] = cls_id
@@ -427,7 +447,7 @@ def finish_beams(hyp_ids, hyp_score, hyp_seq):
     return hyp_ids.gather(1, o[..., None].expand(-1, -1, hyp_ids.shape[2])), hyp_score.gather(1, o)
 
 
-def generate_beam(model, img, X, cfg, kv=None, forced=None, step_logits=None, trace=None):
+def generate_beam(model, img, X, cfg, kv=None, forced=None, step_logits=None, trace=None, pretxt=None):
     """beam search: (ids (B, K, max_len) int64, logprob (B, K) fp32).  Test hooks: forced = (parents (B, max_len - 2, nb) in-clip beam indices,
     words (B, max_len - 2, nb)) replaces the selection of steps 1 .. max_len - 2 (teacher forcing of the beams); step_logits receives each
     step's fp32 [MASK] logits (B * nb, V) before the penalty; trace receives per step (parents (B, nb) in-clip, words (B, nb), the clip's
@@ -436,12 +456,12 @@ def generate_beam(model, img, X, cfg, kv=None, forced=None, step_logits=None, tr
     kv = KV if kv is None else kv
     B, per = img.shape[0], KV_MAX_CLIPS // cfg.num_beams
     if not kv or B <= per:
-        return _generate_beam(model, img, cfg, kv, forced, step_logits, trace)
+        return _generate_beam(model, img, cfg, kv, forced, step_logits, trace, pretxt)
     ids, lps, steps, traces = [], [], [], []
     for s in range(0, B, per):
         sl, tr = ([] if step_logits is not None else None), ([] if trace is not None else None)
         f = None if forced is None else (forced[0][s:s + per], forced[1][s:s + per])
-        i, lp = _generate_beam(model, img[s:s + per], cfg, kv, f, sl, tr)
+        i, lp = _generate_beam(model, img[s:s + per], cfg, kv, f, sl, tr, pretxt)
         ids.append(i)
         lps.append(lp)
         steps.append(sl)
@@ -465,9 +485,9 @@ def _apply_forced(forced, cur, st, clips, nb, dec):
         dec.step_ids[:, 0] = fw.flatten()
 
 
-def _generate_beam(model, img, cfg, kv, forced, step_logits, trace):
+def _generate_beam(model, img, cfg, kv, forced, step_logits, trace, pretxt=None):
     pad_id, eos_id, cls_id = model.pad_token_id, model.sep_token_id, model.cls_token_id
-    feat_img, mask_img = model.enc_img(img)
+    feat_img, mask_img = encode_prefix(model, img, pretxt)
     clips, dev, L, nb = feat_img.shape[0], feat_img.device, cfg.max_len, cfg.num_beams
     R = clips * nb
     if kv:

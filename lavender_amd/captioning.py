@@ -41,8 +41,9 @@ class LAVENDER_Captioning(LAVENDER_Base):
         sampling draws."""
         from . import caption_decode as CD
         batch = defaultdict(lambda: None, batch)
-        if batch["prompt"] is not None and getattr(self.args, "enable_prompt", False):
-            raise NotImplementedError("task tokens / prompts are outside the built paths")
+        pretxt = self._pretxt_spec("cap", batch["prompt"])       # task token / prompt between the video rows and the caption
+        if pretxt is not None:
+            self.cap_prompt_txt_L = 1 if pretxt[0] == "task" else int(pretxt[1][0].shape[-1])
         cfg = CD.make_config(self.args, batch["txt"].shape[1])
         was_training = self.training
         try:
@@ -50,20 +51,34 @@ class LAVENDER_Captioning(LAVENDER_Base):
             with torch.no_grad():
                 self.arena().sync_half_if_stale()
                 if isinstance(cfg, CD.BeamConfig):
-                    return CD.generate_beam(self, batch["img"], batch["txt"].shape[1], cfg)
-                return CD.generate(self, batch["img"], batch["txt"].shape[1], cfg, generator=generator)
+                    return CD.generate_beam(self, batch["img"], batch["txt"].shape[1], cfg, pretxt=pretxt)
+                return CD.generate(self, batch["img"], batch["txt"].shape[1], cfg, generator=generator, pretxt=pretxt)
         finally:
             self.train(was_training)
 
     def encode_forward(self, batch):
-        """model_for_captioning.py:54-95, branch input_ids is None, prompt / task token off."""
+        """model_for_captioning.py:54-95, branch input_ids is None.  With a task token / prompt the pre-text joins the fully visible prefix of
+        the seq2seq mask (causal_from = Lv + Lp), its labels are -1 and its length is recorded in cap_prompt_txt_L."""
         if batch["input_ids"] is not None:
             raise NotImplementedError("the incremental-decoding branch (model_for_captioning.py:96-130) belongs to generation")
         img, txt, mask, ans_mtm = batch["img"], batch["txt"], batch["mask"], batch["ans_mtm"]
+        prompt = batch["prompt"]
         (_B, _T, _, _H, _W) = img.shape
         _h, _w = _H // 32, _W // 32
-        feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img, txt, mask)
-        ans_mtm, _, feat_txt = self.prepro_txt_inputs(ans_mtm, mask_txt, feat_txt, task_name="cap", prompt=batch["prompt"])
-        out, _ = self.go_cross(feat_img, mask_img, feat_txt, mask_txt, attn_mask_type=batch["attn_mask_type"] or "seq2seq")
+        feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img, txt, mask, task_name="cap", prompt=prompt)
+        ans_mtm, _, feat_txt = self.prepro_txt_inputs(ans_mtm, mask_txt, feat_txt, task_name="cap", prompt=prompt)
+        if prompt is not None and getattr(self.args, "enable_prompt", False):
+            _L = len(prompt[0])
+            self.cap_prompt_txt_L = _L
+        elif getattr(self.args, "enable_task_token", False):
+            _L = 1
+            self.cap_prompt_txt_L = _L
+        else:
+            _L = 0
+            assert self.cap_prompt_txt_L == _L
+        ans_mtm[:, :_L] = -1
+        mask_pretxt = torch.ones_like(mask_txt)[:, :_L] if _L > 0 else None
+        out, _ = self.go_cross(feat_img, mask_img, feat_txt, mask_txt, attn_mask_type=batch["attn_mask_type"] or "seq2seq",
+                               mask_pretxt=mask_pretxt)
         out = self.fc_mtm(out[:, (1 + _h * _w) * _T:])
         return {"out": out, "ans": ans_mtm}

@@ -204,15 +204,31 @@ extern "C" int lav_video_embed_bwd(void* stream, int B, int T, int hw, int Hd, c
 }
 
 // ---- BERT text embedding (+LN eps, +dropout) ---------------------------------------------------------
+// Lp > 0 (lav_text_embed_pre_fwd): text j's block of `out` is Lp + X rows [pre-text ; text]; text row r = j * X + x lands at row
+// r + (j + 1) * Lp, its dropout key and mean / rstd index stay r (the bits of lav_text_embed_fwd).  The waves past the n * X text rows copy
+// the n * Lp pre-text rows from pre + j * pre_stride.
 template <int MAXC>
 __global__ __launch_bounds__(256) void text_embed_fwd_kernel(int n, int X, int Hd, const int64_t* ids, const float* word, const float* pos,
                                                             const float* type0, const float* gamma, const float* beta, float eps,
                                                             float p, uint32_t seed, uint32_t thresh, bf16_t* out, float* mean_o,
-                                                            float* rstd_o) {
+                                                            float* rstd_o, int Lp, const bf16_t* pre, long pre_stride) {
     const int lane = threadIdx.x & 63;
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= (long)n * X) return;
+    if (r >= (long)n * X) {
+        const long q = r - (long)n * X;
+        if (q >= (long)n * Lp) return;
+        const long j = q / Lp, pp = q - j * Lp;
+        const bf16_t* src = pre + j * pre_stride + pp * Hd;
+        bf16_t* dst = out + (j * (Lp + X) + pp) * Hd;
+#pragma unroll
+        for (int it = 0; it < MAXC; ++it) {
+            const int col = (it * 64 + lane) * 8;
+            if (col < Hd) *(uint4*)(dst + col) = *(const uint4*)(src + col);
+        }
+        return;
+    }
     const int xp = r % X;
+    const long ro = r + (r / X + 1) * Lp;               // output row j * (Lp + X) + Lp + x (r when Lp = 0)
     const long id = ids[r];
     float v[MAXC][8];
     float s = 0.f;
@@ -246,10 +262,77 @@ __global__ __launch_bounds__(256) void text_embed_fwd_kernel(int n, int X, int H
                 y[k] = (v[it][k] - mean) * rstd * gamma[col + k] + beta[col + k];
                 if (p > 0.f) y[k] = lav_keep(seed, (uint32_t)r * (uint32_t)Hd + (uint32_t)(col + k), thresh) ? y[k] * inv : 0.f;
             }
-            *(uint4*)(out + r * Hd + col) = pack8(y);
+            *(uint4*)(out + ro * Hd + col) = pack8(y);
         }
     }
     if (lane == 0) { mean_o[r] = mean; rstd_o[r] = rstd; }
+}
+
+// Pre-text gradient of one pre-text row p over the texts [s0, s1e) of a block (the blocks past the X text positions of text_embed_bwd_kernel).
+//   pre_stride != 0 (a block per text): d_pre is bf16 (n, Lp, Hd) and takes text j's rows as they are.
+//   pre_stride == 0 (one broadcast block): sum_j dout[j, p] in fp32, in a FIXED order -- each wave its texts s0 + wave, s0 + wave + 4, ...
+//   in turn, then waves 0 + 1 + 2 + 3 -- and no atomics: run to run the same bits.  One group (gridDim.y == 1) finishes here (mode 0: fp32
+//   d_pre[p] += sum, mode 1: bf16 d_pre[p] = sum); several groups leave fp32 partials part[group][p] for text_pre_grad_finish_kernel.
+__device__ __forceinline__ void text_pre_grad(int n, int X, int Hd, const bf16_t* dout, int Lp, int p, int s0, int s1e, long pre_stride,
+                                              void* d_pre, int mode, float* part, float* red) {
+    constexpr int MAXC = 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (pre_stride != 0) {
+        for (int sq = s0 + wave; sq < s1e; sq += 4) {
+            const bf16_t* src = dout + ((long)sq * (Lp + X) + p) * Hd;
+            bf16_t* dst = (bf16_t*)d_pre + ((long)sq * Lp + p) * Hd;
+#pragma unroll
+            for (int it = 0; it < MAXC; ++it) {
+                const int col = (it * 64 + lane) * 8;
+                if (col < Hd) *(uint4*)(dst + col) = *(const uint4*)(src + col);
+            }
+        }
+        return;
+    }
+    float a[MAXC][8];
+#pragma unroll
+    for (int it = 0; it < MAXC; ++it)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[it][k] = 0.f;
+    for (int sq = s0 + wave; sq < s1e; sq += 4) {
+        const bf16_t* src = dout + ((long)sq * (Lp + X) + p) * Hd;
+#pragma unroll
+        for (int it = 0; it < MAXC; ++it) {
+            const int col = (it * 64 + lane) * 8;
+            if (col < Hd) {
+                float d[8];
+                unpack8(*(const uint4*)(src + col), d);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) a[it][k] += d[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < MAXC; ++it) {
+        const int col = (it * 64 + lane) * 8;
+        if (col < Hd)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) red[wave * Hd + col + k] = a[it][k];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < Hd; c += 256) {
+        const float v = ((red[c] + red[Hd + c]) + red[2 * Hd + c]) + red[3 * Hd + c];
+        if (gridDim.y > 1) part[((long)blockIdx.y * Lp + p) * Hd + c] = v;
+        else if (mode == 0) ((float*)d_pre)[(long)p * Hd + c] += v;
+        else ((bf16_t*)d_pre)[(long)p * Hd + c] = f2bf(v);
+    }
+}
+
+// the groups' partials of the broadcast pre-text gradient, summed in group order: one block per pre-text row
+__global__ __launch_bounds__(256) void text_pre_grad_finish_kernel(int groups, int Lp, int Hd, const float* __restrict__ part, void* d_pre,
+                                                                  int mode) {
+    const int p = blockIdx.x;
+    for (int c = threadIdx.x; c < Hd; c += 256) {
+        float v = 0.f;
+        for (int g = 0; g < groups; ++g) v += part[((long)g * Lp + p) * Hd + c];
+        if (mode == 0) ((float*)d_pre)[(long)p * Hd + c] += v;
+        else ((bf16_t*)d_pre)[(long)p * Hd + c] = f2bf(v);
+    }
 }
 
 // backward: one block per (token position, group of sequences): the rows of a block share the position embedding, so
@@ -261,12 +344,17 @@ __global__ __launch_bounds__(256) void text_embed_bwd_kernel(int n, int X, int H
                                                             const float* pos, const float* type0, const float* gamma,
                                                             const float* mean_i, const float* rstd_i, float p, uint32_t seed,
                                                             uint32_t thresh, float* d_word, float* d_pos, float* d_type0,
-                                                            float* dgamma, float* dbeta) {
+                                                            float* dgamma, float* dbeta, int Lp, long pre_stride, void* d_pre,
+                                                            int d_pre_mode, float* part) {
     extern __shared__ float red[];                        // [4 waves][3][Hd]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int xp = blockIdx.x;
     const int per = (n + gridDim.y - 1) / gridDim.y;
     const int s0 = blockIdx.y * per, s1e = min(n, s0 + per);
+    if (xp >= X) {                                        // pre-text row xp - X (lav_text_embed_pre_bwd)
+        text_pre_grad(n, X, Hd, dout, Lp, xp - X, s0, s1e, pre_stride, d_pre, d_pre_mode, part, red);
+        return;
+    }
     const float inv = p > 0.f ? 1.f / (1.f - p) : 1.f;
     float a_g[MAXC][8], a_b[MAXC][8], a_x[MAXC][8];
 #pragma unroll
@@ -284,7 +372,7 @@ __global__ __launch_bounds__(256) void text_embed_bwd_kernel(int n, int X, int H
             const int col = (it * 64 + lane) * 8;
             if (col < Hd) {
                 float d[8];
-                uint4 du = *(const uint4*)(dout + r * Hd + col); unpack8(du, d);
+                uint4 du = *(const uint4*)(dout + (r + (long)(sq + 1) * Lp) * Hd + col); unpack8(du, d);   // row sq * (Lp + X) + Lp + xp
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     if (p > 0.f) d[k] = lav_keep(seed, (uint32_t)r * (uint32_t)Hd + (uint32_t)(col + k), thresh) ? d[k] * inv : 0.f;
@@ -342,8 +430,23 @@ extern "C" int lav_text_embed_fwd(void* stream, int n, int X, int Hd, const int6
     LAV_REQUIRE(ids && word && pos && type0 && gamma && beta && out && mean && rstd, "lav_text_embed_fwd: null pointer");
     long rows = (long)n * X;
     hipLaunchKernelGGL(text_embed_fwd_kernel<2>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, n, X, Hd, ids, word,
-                       pos, type0, gamma, beta, eps, dropout_p, seed, lav_drop_thresh(dropout_p), (bf16_t*)out, mean, rstd);
+                       pos, type0, gamma, beta, eps, dropout_p, seed, lav_drop_thresh(dropout_p), (bf16_t*)out, mean, rstd, 0,
+                       (const bf16_t*)nullptr, 0L);
     return lav_check_launch("lav_text_embed_fwd");
+}
+
+extern "C" int lav_text_embed_pre_fwd(void* stream, int n, int Lp, int X, int Hd, const int64_t* ids, const float* word, const float* pos,
+                                      const float* type0, const float* gamma, const float* beta, float eps, float dropout_p, uint32_t seed,
+                                      const void* pre, long pre_stride, void* out, float* mean, float* rstd) {
+    LAV_REQUIRE(n > 0 && X > 0 && Lp >= 0 && Hd % 8 == 0 && Hd <= 1024, "lav_text_embed_pre_fwd: bad shape n=%d Lp=%d X=%d Hd=%d", n, Lp, X, Hd);
+    LAV_REQUIRE(ids && word && pos && type0 && gamma && beta && out && mean && rstd && (Lp == 0 || pre), "lav_text_embed_pre_fwd: null pointer");
+    LAV_REQUIRE(pre_stride == 0 || pre_stride == (long)Lp * Hd, "lav_text_embed_pre_fwd: pre_stride must be 0 (one broadcast block) or Lp * Hd (a block per text), got %ld", pre_stride);
+    LAV_REQUIRE(Lp == 0 || ((uintptr_t)pre & 15) == 0, "lav_text_embed_pre_fwd: pre must be 16-byte aligned");
+    long rows = (long)n * (X + Lp);
+    hipLaunchKernelGGL(text_embed_fwd_kernel<2>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, n, X, Hd, ids, word,
+                       pos, type0, gamma, beta, eps, dropout_p, seed, lav_drop_thresh(dropout_p), (bf16_t*)out, mean, rstd, Lp,
+                       (const bf16_t*)pre, pre_stride);
+    return lav_check_launch("lav_text_embed_pre_fwd");
 }
 
 extern "C" int lav_text_embed_bwd(void* stream, int n, int X, int Hd, const int64_t* ids, const void* dout, const float* word,
@@ -357,8 +460,35 @@ extern "C" int lav_text_embed_bwd(void* stream, int n, int X, int Hd, const int6
     (void)rows;
     hipLaunchKernelGGL(text_embed_bwd_kernel<2>, dim3(X, groups), dim3(256), (size_t)12 * Hd * sizeof(float), (hipStream_t)stream, n, X, Hd, ids,
                        (const bf16_t*)dout, word, pos, type0, gamma, mean, rstd, dropout_p, seed, lav_drop_thresh(dropout_p), d_word,
-                       d_pos, d_type0, dgamma, dbeta);
+                       d_pos, d_type0, dgamma, dbeta, 0, 0L, (void*)nullptr, 0, (float*)nullptr);
     return lav_check_launch("lav_text_embed_bwd");
+}
+
+extern "C" int lav_text_embed_pre_bwd(void* stream, int n, int Lp, int X, int Hd, const int64_t* ids, const void* dout, const float* word,
+                                      const float* pos, const float* type0, const float* gamma, const float* mean, const float* rstd,
+                                      float dropout_p, uint32_t seed, float* d_word, float* d_pos, float* d_type0, float* dgamma,
+                                      float* dbeta, long pre_stride, void* d_pre, int d_pre_mode) {
+    LAV_REQUIRE(n > 0 && X > 0 && Lp >= 0 && Hd % 8 == 0 && Hd <= 1024, "lav_text_embed_pre_bwd: bad shape n=%d Lp=%d X=%d Hd=%d", n, Lp, X, Hd);
+    LAV_REQUIRE(ids && dout && d_word && d_pos && d_type0 && dgamma && dbeta && (Lp == 0 || d_pre), "lav_text_embed_pre_bwd: null pointer");
+    LAV_REQUIRE(pre_stride == 0 || pre_stride == (long)Lp * Hd, "lav_text_embed_pre_bwd: pre_stride must be 0 or Lp * Hd, got %ld", pre_stride);
+    LAV_REQUIRE(d_pre_mode == 0 || d_pre_mode == 1, "lav_text_embed_pre_bwd: d_pre_mode must be 0 (fp32 accumulate) or 1 (bf16 rows)");
+    LAV_REQUIRE(pre_stride == 0 || d_pre_mode == 1, "lav_text_embed_pre_bwd: a pre-text block per text (pre_stride = Lp * Hd) returns bf16 rows (d_pre_mode 1)");
+    const int groups = n >= 32 ? 8 : (n >= 8 ? 2 : 1);
+    float* part = nullptr;
+    const bool finish = Lp > 0 && pre_stride == 0 && groups > 1;
+    if (finish) {
+        size_t cap = 0;
+        part = (float*)lav_ws_get(stream, LAV_WS_LN_PARTIALS, (size_t)groups * Lp * Hd * sizeof(float), &cap);
+        if (!part) return LAV_E_WORKSPACE;
+    }
+    hipLaunchKernelGGL(text_embed_bwd_kernel<2>, dim3(X + Lp, groups), dim3(256), (size_t)12 * Hd * sizeof(float), (hipStream_t)stream, n, X,
+                       Hd, ids, (const bf16_t*)dout, word, pos, type0, gamma, mean, rstd, dropout_p, seed, lav_drop_thresh(dropout_p), d_word,
+                       d_pos, d_type0, dgamma, dbeta, Lp, pre_stride, d_pre, d_pre_mode, part);
+    if (int rc = lav_check_launch("lav_text_embed_pre_bwd")) return rc;
+    if (!finish) return LAV_OK;
+    hipLaunchKernelGGL(text_pre_grad_finish_kernel, dim3(Lp), dim3(256), 0, (hipStream_t)stream, groups, Lp, Hd, (const float*)part, d_pre,
+                       d_pre_mode);
+    return lav_check_launch("lav_text_embed_pre_bwd (finish)");
 }
 
 // ---- row gather / gather-sum -------------------------------------------------------------------------

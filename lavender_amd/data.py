@@ -159,6 +159,19 @@ class FrameDecoder:
         self.close()
 
 
+# the prompt_text of each caller's dataset in the reference (enable_prompt); "qamc" takes args.size_option
+PROMPT_TEXTS = {
+    "pretrain_vtm": "is the video-text paired, true or false?",            # main_pretrain_mlm.py:28-29
+    "pretrain_cap": "write a description about the video.",                # main_pretrain_mlm.py:35-36
+    "retrieval": "is the video-text paired, true or false?",               # main_retrieval_mlm.py:26-27
+    "retmc": "is the video-text matched, true or false?",                  # main_retmc_mlm.py:55-56
+    "qaoe": "answer the question about the video.",                        # main_qaoe_mlm.py:40-42
+    "qaoe_fib": "fill in the mask to complete the sentence.",              # main_qaoe_mlm_lsmdc_fib.py:18-19
+    "caption": "write a description about the video.",                     # main_caption.py:34-35
+    "qamc": lambda size_option: "which answer is correct, from " + f"{list(range(size_option))}?",   # main_qamc_mlm.py:90-92
+}
+
+
 class Dataset_Base:
     """dataset.py:18-276 for the pretrain path."""
 
@@ -190,6 +203,20 @@ class Dataset_Base:
     def replace_cls_w_mask(self, txt, mask):
         one = torch.LongTensor([1])
         return torch.cat([self.mask_token_id * one, txt[1:]], -1), torch.cat([one, mask[1:]], -1)
+
+    # ---- prompt (dataset.py:72-81): [CLS] + tokens of prompt_text + [SEP], all ones as mask ------------------------------
+    @property
+    def prompt_text(self):
+        """the caller's prompt (PROMPT_TEXTS lists the reference's); a dataset class for enable_prompt overrides this"""
+        raise NotImplementedError(f"{type(self).__name__} has no prompt_text (see lavender_amd.data.PROMPT_TEXTS)")
+
+    def get_prompt(self, prompt_text=None):
+        if prompt_text is None:
+            prompt_text = self.prompt_text
+        toks = self.tokzr.tokenize(prompt_text)
+        txt = [self.cls_token_id] + self.tokzr.convert_tokens_to_ids(toks) + [self.sep_token_id]
+        mask = torch.LongTensor([1 if w != self.pad_token_id else w for w in txt])
+        return torch.LongTensor(txt), mask
 
     def str2txt(self, s):
         txt = self.tokzr.encode(s, padding="max_length", max_length=self.args.size_txt, truncation=True)
@@ -338,6 +365,20 @@ class Dataset_Pretrain_MLM(Dataset_Pretrain):
     def str2txt(self, s):
         txt, mask = super().str2txt(s)
         return self.append_mask_tok2txt(txt, mask)
+
+    @property
+    def vtm_prompt_text(self):
+        return PROMPT_TEXTS["pretrain_vtm"]
+
+    def get_vtm_prompt(self):
+        return self.get_prompt(prompt_text=self.vtm_prompt_text)
+
+    @property
+    def cap_prompt_text(self):
+        return PROMPT_TEXTS["pretrain_cap"]
+
+    def get_cap_prompt(self):
+        return self.get_prompt(prompt_text=self.cap_prompt_text)
 
 
 class _Sampler:

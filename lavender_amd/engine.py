@@ -673,6 +673,90 @@ class TextEmbedFn(torch.autograd.Function):
         return None, None, None, None
 
 
+class PreTextEmbedFn(torch.autograd.Function):
+    """TextEmbedFn behind a pre-text segment (get_pretxt / prepro_txt_inputs, model.py:250-307): (n, Lp + X, H) rows [pre-text ; text] from
+    ONE kernel (lav_text_embed_pre_fwd) -- under a fusion_tail_hint of n * (Lp + X) rows they land behind the video rows, so video, pre-text
+    and text stay one buffer.  The pre-text is either
+      task = (emb_task, row): the task token, read in place from the arena's bf16 copy of that row; its gradient (the sum over the n texts,
+             fixed-order fp32) is accumulated straight into G(emb_task)[row];
+      pre: the bf16 (1, Lp, H) (broadcast) or (n, Lp, H) (a block per text) prompt features, an autograd input: its gradient is returned as
+             bf16 rows to the prompt's own TextEmbedFn.
+    The text rows are bit-identical to TextEmbedFn's for the same ids and seed."""
+
+    @staticmethod
+    def forward(ctx, anchor, ids, emb, dropout_p, pre, task):
+        n, X = ids.shape
+        Hd = emb.word_embeddings.weight.shape[1]
+        ids = ids.contiguous()
+        if task is not None:
+            param, row = task
+            Lp, stride, src = 1, 0, W16(param)[row]
+        else:
+            Lp = pre.shape[-2]
+            src = pre.contiguous()
+            stride = 0 if src.shape[0] == 1 else Lp * Hd
+            assert src.dtype == bf16 and src.shape[-1] == Hd and src.shape[0] in (1, n), (tuple(src.shape), n)
+        seed = K.next_seed()
+        pend, out = _fusion_tail["pending"], None
+        _fusion_tail["pending"] = None
+        if pend is not None and pend[2] == n * (Lp + X) and pend[0].shape[1] == Hd and pend[0].device == ids.device:
+            out = pend[0][pend[1]:]                              # the tail of the video rows' buffer
+        out, mean, rstd = K.text_embed_pre_fwd(ids, n, Lp, X, Hd, emb.word_embeddings.weight.data, emb.position_embeddings.weight.data,
+                                               emb.token_type_embeddings.weight.data, emb.LayerNorm.weight.data, emb.LayerNorm.bias.data,
+                                               emb.LayerNorm.eps, dropout_p, seed, src, stride, out=out)
+        ctx.emb, ctx.p, ctx.seed, ctx.task, ctx.pre_meta = emb, dropout_p, seed, task, (Lp, stride, None if pre is None else tuple(src.shape))
+        ctx.save_for_backward(ids, mean, rstd)
+        return out.view(n, Lp + X, Hd)
+
+    @staticmethod
+    def backward(ctx, dout):
+        emb = ctx.emb
+        ids, mean, rstd = ctx.saved_tensors
+        n, X = ids.shape
+        Lp, stride, pre_shape = ctx.pre_meta
+        Hd = emb.word_embeddings.weight.shape[1]
+        dout = dout.contiguous()
+        if ctx.task is not None:
+            param, row = ctx.task
+            d_pre, mode = G(param)[row], 0                     # G: a first-touch unit is made valid zero before this accumulate
+        else:
+            d_pre, mode = torch.empty(pre_shape, dtype=bf16, device=dout.device), 1
+        args = (ids, dout, n, Lp, X, Hd, emb.word_embeddings.weight.data, emb.position_embeddings.weight.data,
+                emb.token_type_embeddings.weight.data, emb.LayerNorm.weight.data, mean, rstd, ctx.p, ctx.seed,
+                G(emb.word_embeddings.weight), G(emb.position_embeddings.weight), G(emb.token_type_embeddings.weight),
+                G(emb.LayerNorm.weight), G(emb.LayerNorm.bias), stride, d_pre, mode)
+        if _DW_SIDE and dout.is_cuda:
+            # the stream placement of TextEmbedFn.backward (see there).  A prompt's d_pre is written on the weight-gradient stream too; its one
+            # reader is the prompt's own TextEmbedFn.backward, which runs on that stream after this kernel (FIFO order).
+            side = dw_stream(dout.device)
+            _arm_join()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                K.text_embed_pre_bwd(*args)
+            for t in (ids, dout, mean, rstd, d_pre):
+                t.record_stream(side)
+        else:
+            K.text_embed_pre_bwd(*args)
+        return None, None, None, None, (d_pre if ctx.task is None else None), None
+
+
+class TaskRowFn(torch.autograd.Function):
+    """The task-token row emb_task[row] as bf16 (1, H) features for a caller that concatenates it itself (features that did not come from
+    go_feat); the backward sums the incoming rows into G(emb_task)[row] (lav_colsum_bf16)."""
+
+    @staticmethod
+    def forward(ctx, anchor, param, row):
+        ctx.param, ctx.row = param, row
+        return W16(param)[row:row + 1].clone()
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        Hd = dy.shape[-1]
+        K.colsum(dy.view(-1, Hd), dy.numel() // Hd, Hd, G(ctx.param)[ctx.row])
+        return None, None, None
+
+
 def pair_index(B, Lv, nt, X, vi, ti):
     """(n, L) int32 map: row r of pair k's sequence [video rows of clip vi[k] | text rows of text ti[k]] -> row of the un-expanded
     source [B * Lv video rows ; nt * X text rows] (T.cat at model.py:235 over the pair list of main_pretrain_mlm.py:74-111 /

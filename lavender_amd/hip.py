@@ -529,6 +529,31 @@ def text_embed_bwd(ids, dout, n, X, Hd, word, pos, type0, gamma, mean, rstd, dro
                                      _p(d_type0), _p(dgamma), _p(dbeta)), "lav_text_embed_bwd")
 
 
+def text_embed_pre_fwd(ids, n, Lp, X, Hd, word, pos, type0, gamma, beta, eps, dropout_p, seed, pre, pre_stride, out=None):
+    """lav_text_embed_pre_fwd: (n * (Lp + X), Hd) bf16 rows [pre-text ; text] per text; pre: bf16 rows read from pre + j * pre_stride"""
+    dev = ids.device
+    if out is None:
+        out = torch.empty((n * (Lp + X), Hd), dtype=bf16, device=dev)
+    assert out.numel() >= n * (Lp + X) * Hd and out.is_contiguous()
+    mean = torch.empty(n * X, dtype=torch.float32, device=dev)
+    rstd = torch.empty(n * X, dtype=torch.float32, device=dev)
+    L.check(L.lib.lav_text_embed_pre_fwd(_s(), n, Lp, X, Hd, _p(ids), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta), float(eps),
+                                         float(dropout_p), int(seed) & 0xFFFFFFFF, _p(pre) if Lp else None, int(pre_stride), _p(out),
+                                         _p(mean), _p(rstd)), "lav_text_embed_pre_fwd")
+    return out, mean, rstd
+
+
+def text_embed_pre_bwd(ids, dout, n, Lp, X, Hd, word, pos, type0, gamma, mean, rstd, dropout_p, seed, d_word, d_pos, d_type0,
+                       dgamma, dbeta, pre_stride, d_pre, d_pre_mode):
+    """lav_text_embed_pre_bwd: d_pre_mode 0 accumulates the summed pre-text gradient into the fp32 rows d_pre, 1 writes bf16 rows"""
+    if Lp and pre_stride == 0 and n >= 8:
+        ensure_workspace(WS_LN_PARTIALS, 8 * Lp * Hd * 4)          # the texts' fp32 partials of the broadcast pre-text gradient
+    L.check(L.lib.lav_text_embed_pre_bwd(_s(), n, Lp, X, Hd, _p(ids), _p(dout), _p(word), _p(pos), _p(type0), _p(gamma), _p(mean),
+                                         _p(rstd), float(dropout_p), int(seed) & 0xFFFFFFFF, _p(d_word), _p(d_pos), _p(d_type0),
+                                         _p(dgamma), _p(dbeta), int(pre_stride), _p(d_pre) if Lp else None, int(d_pre_mode)),
+            "lav_text_embed_pre_bwd")
+
+
 def _pair_index(idx, bound, what, device):
     """int32 device copy of a pair-list index, every entry checked against [0, bound) on the host first: the kernel reads the mask rows it names
     without a bounds check.  Host arrays (what the model passes) cost no device read; a device tensor is read back once."""

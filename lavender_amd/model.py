@@ -81,6 +81,12 @@ class EncTxt(nn.Module):
         p = self.emb_txt.dropout_p if self.training else 0.0
         return E.TextEmbedFn.apply(arena.anchor, txt, self.emb_txt, p)
 
+    def embed_with_pretxt(self, txt, pre=None, task=None):
+        """(n, Lp + X, H) [pre-text ; embedded text]: pre = prompt features (1 or n, Lp, H), or task = (emb_task, row) (engine.PreTextEmbedFn)"""
+        arena = self._arena_of()
+        p = self.emb_txt.dropout_p if self.training else 0.0
+        return E.PreTextEmbedFn.apply(arena.anchor, txt, self.emb_txt, p, pre, task)
+
 
 class _AttentionsNotMaterialised:
     """Second return value of go_cross / go_cross_pairs.  The reference asks the HF encoder for output_attentions=True
@@ -176,11 +182,25 @@ class LAVENDER_Base(nn.Module):
         """get_extended_attention_mask as used at model.py:136,239: (B,L) 0/1 -> additive (B,1,1,L)."""
         return (1.0 - mask[:, None, None, :].to(dtype)) * torch.finfo(dtype).min
 
-    def go_feat(self, img, txt, mask, odr=None, vt_mask=None, attn_mask_type="full"):
+    def go_feat(self, img, txt, mask, odr=None, vt_mask=None, attn_mask_type="full", task_name=None, prompt=None):
+        """model.py:186-192.  task_name / prompt (this engine's addition): when get_pretxt would add a pre-text for them, feat_txt comes back
+        as (n, Lp + X, H) [pre-text ; text] rows written by one kernel behind the video rows -- prepro_txt_inputs with the same task_name /
+        prompt then prepends the ids and masks only.  mask is returned as given, as in the reference."""
         self.arena().sync_half_if_stale()
-        E.fusion_tail_hint(txt.shape[0] * txt.shape[1])       # feat_img and feat_txt land in ONE buffer: no T.cat in front of the fusion encoder
+        spec = self._pretxt_spec(task_name, prompt) if (task_name is not None or prompt is not None) else None
+        pre, task, Lp = None, None, 0
+        if spec is not None and spec[0] == "task":
+            task, Lp = (self.emb_task, spec[1]), 1
+        elif spec is not None:
+            pre = self._embed_prompt(spec[1][0], txt.device)   # before the tail hint: this small embedding is not part of the one buffer
+            Lp = pre.shape[1]
+        E.fusion_tail_hint(txt.shape[0] * (Lp + txt.shape[1]))   # feat_img and feat_txt land in ONE buffer: no T.cat in front of the fusion encoder
         feat_img, mask_img = self.enc_img(img, odr, vt_mask)
-        feat_txt = self.enc_txt(txt, mask_txt=mask, attn_mask_type=attn_mask_type)
+        if spec is None:
+            feat_txt = self.enc_txt(txt, mask_txt=mask, attn_mask_type=attn_mask_type)
+        else:
+            feat_txt = self.enc_txt.embed_with_pretxt(txt, pre, task)
+            feat_txt._lav_pretxt = spec
         E.fusion_tail_hint(0)
         return feat_img, mask_img, feat_txt, mask
 
@@ -188,17 +208,16 @@ class LAVENDER_Base(nn.Module):
         """model.py:194-221.  "full": (B, L) concatenation of the 0/1 masks.  "seq2seq" (captioning): the (B, L, L) mask of
         model.py:208-218 -- every query sees the video keys (by mask_img), text queries additionally see the text keys up to
         themselves, video queries see no text key.  The attention kernels take it as (key mask, number of prefix keys)."""
-        if mask_pretxt is not None:
-            raise NotImplementedError("pre-text (prompt / task-token) masks (model.py:200-203) are outside the built paths")
+        full_mask = mask_img if mask_pretxt is None else torch.cat([mask_img, mask_pretxt.to(mask_img.device, mask_img.dtype)], dim=1)
         if attn_mask_type == "seq2seq":
-            _B, _Lv = mask_img.shape
+            _B, _Lfull = full_mask.shape                       # the pre-text belongs to the fully visible prefix
             _Lt = mask_txt.shape[1]
-            _L = _Lv + _Lt
+            _L = _Lfull + _Lt
             mask = torch.zeros((_B, _L, _L), dtype=torch.long, device=mask_img.device)
-            mask[:, :, :_Lv] = mask_img[:, None, :]
-            mask[:, _Lv:, _Lv:] = torch.tril(torch.ones((_Lt, _Lt), dtype=torch.long, device=mask_img.device))
+            mask[:, :, :_Lfull] = full_mask[:, None, :]
+            mask[:, _Lfull:, _Lfull:] = torch.tril(torch.ones((_Lt, _Lt), dtype=torch.long, device=mask_img.device))
             return mask
-        return torch.cat([mask_img, mask_txt], dim=1)
+        return torch.cat([full_mask, mask_txt], dim=1)
 
     def _encode(self, feat, mask, causal_from=0, pair=None):
         """feat (n, L, H) bf16, mask (n, L) 0/1 key mask -> last_hidden_state (n, L, H).  causal_from > 0: seq2seq mask with that
@@ -245,16 +264,21 @@ class LAVENDER_Base(nn.Module):
         return src, tuple(pair)
 
     def go_cross(self, feat_img, mask_img, feat_txt, mask_txt, attn_mask_type="full", feat_pretxt=None, mask_pretxt=None):
+        """model.py:223-245.  feat_pretxt (n, Lp, H): placed between the video and the text rows (one copy of the text rows; go_feat's
+        pre-text path writes them in place instead).  mask_pretxt (n, Lp): the key mask of pre-text rows that feat_txt already carries in
+        front of its text rows (captioning, model_for_captioning.py:83-92)."""
         if feat_pretxt is not None:
-            raise NotImplementedError("prompt / task-token pre-text (model.py:228-232) is outside the pretrain hot path")
+            feat_txt = torch.cat([feat_pretxt.to(feat_txt.dtype).expand(feat_txt.shape[0], -1, -1), feat_txt], dim=1)
         n = feat_img.shape[0]
         ident = np.arange(n)
         feat, pair = self._pair_source(feat_img, feat_txt, ident, ident)
         if attn_mask_type == "seq2seq":
-            # (B, L, L) mask of get_attn_mask in kernel form: video keys by mask_img, text keys all valid but causal
-            key_mask = torch.cat([mask_img, torch.ones_like(mask_txt)], dim=1)
-            return self._encode(feat, key_mask, causal_from=mask_img.shape[1], pair=pair), _NO_ATTN
-        mask = self.get_attn_mask(mask_img, mask_txt, attn_mask_type=attn_mask_type)
+            # (B, L, L) mask of get_attn_mask in kernel form: video (and pre-text) keys by their masks, text keys all valid but causal
+            prefix = mask_img if mask_pretxt is None else torch.cat([mask_img, mask_pretxt.to(mask_img.device, mask_img.dtype)], dim=1)
+            key_mask = torch.cat([prefix, torch.ones_like(mask_txt)], dim=1)
+            assert key_mask.shape[1] == feat_img.shape[1] + feat_txt.shape[1], "mask and feat must have the same length"
+            return self._encode(feat, key_mask, causal_from=prefix.shape[1], pair=pair), _NO_ATTN
+        mask = self.get_attn_mask(mask_img, mask_txt, attn_mask_type=attn_mask_type, mask_pretxt=mask_pretxt)
         assert feat_img.shape[1] + feat_txt.shape[1] == mask.shape[1], f"mask and feat must have the same length, got {feat_img.shape[1] + feat_txt.shape[1]} vs. {mask.shape[1]}"
         return self._encode(feat, mask, pair=pair), _NO_ATTN
 
@@ -267,11 +291,81 @@ class LAVENDER_Base(nn.Module):
         mask = K.pair_key_mask(mask_img, mask_txt, vi, ti)         # (n, L) int32: get_attn_mask("full") over the pair list, one launch
         return self._encode(feat, mask, pair=pair), _NO_ATTN
 
+    # ---- pre-text: task token / prompt (model.py:247-307) ---------------------------------------------------------
+    def _pretxt_spec(self, task_name=None, prompt=None):
+        """what get_pretxt adds, with its precedence: ("task", row of emb_task) when args.enable_task_token, else ("prompt", (ids, mask))
+        when a prompt is given and args.enable_prompt, else None"""
+        if getattr(self.args, "enable_task_token", False):
+            assert task_name is not None, "enable_task_token: the batch must name its task (batch['task_name'])"
+            assert task_name in self.task_tok2id, f"unknown task {task_name!r} (task_tok2id: {sorted(self.task_tok2id)})"
+            return ("task", self.task_tok2id[task_name])
+        if prompt is not None and getattr(self.args, "enable_prompt", False):
+            return ("prompt", prompt)
+        return None
+
+    def _embed_prompt(self, prompt_txt, device):
+        """a prompt's features, embedded ONCE per call (dropout included) with the text embedding: (1, Lp, H) for a 1-D prompt (broadcast to
+        every text), (n, Lp, H) for a 2-D one.  The reference's batched callers do the same (enc_txt(prompt), then expand); its per-pair loops
+        (pretrain VTM, retrieval) embed the prompt once per pair and so draw a fresh dropout mask per pair -- the difference vanishes in eval."""
+        ids = prompt_txt.to(device, non_blocking=True)
+        return self.enc_txt(ids.unsqueeze(0) if ids.dim() == 1 else ids)
+
+    def prepro_pretxt(self, task_or_prompt_txt):
+        """model.py:247-248: the pre-text ids as they enter the returned txt (the QA callers override this with -1 labels)"""
+        return task_or_prompt_txt
+
+    def _pretxt_ids(self, spec, mask_txt):
+        """(ids, mask) of the pre-text, shaped like mask_txt's leading dimensions (model.py:253-290 without the features)"""
+        txt_dim, dev = mask_txt.dim(), mask_txt.device
+        if spec[0] == "task":
+            ids = torch.zeros(1, device=dev, dtype=mask_txt.dtype)
+            m = torch.ones(1, device=dev, dtype=mask_txt.dtype)
+            if txt_dim > 1:
+                ids, m = ids.unsqueeze(0).expand(mask_txt.shape[0], -1), m.unsqueeze(0).expand(mask_txt.shape[0], -1)
+            return self.prepro_pretxt(ids), m
+        ids, m = spec[1]
+        ids, m = ids.to(dev, non_blocking=True), m.to(dev, non_blocking=True)
+        if txt_dim > 1 and ids.dim() == 1:
+            ids, m = ids.unsqueeze(0).expand(mask_txt.shape[0], -1), m.unsqueeze(0).expand(mask_txt.shape[0], -1)
+        elif txt_dim > 1 and ids.dim() > 1:
+            assert mask_txt.shape[0] == ids.shape[0]
+        elif not (txt_dim == 1 and ids.dim() == 1):
+            raise ValueError(f"txt dim: {txt_dim}, prompt_txt dim {ids.dim()}")
+        return self.prepro_pretxt(ids), m
+
+    def get_pretxt(self, mask_txt, task_name=None, prompt=None):
+        """model.py:250-290: (ids, mask, features) of the pre-text, or (None, None, None).  The features here are a separate tensor for a caller
+        that concatenates them itself; go_feat(..., task_name=, prompt=) writes them in place instead."""
+        spec = self._pretxt_spec(task_name, prompt)
+        if spec is None:
+            return None, None, None
+        ids, m = self._pretxt_ids(spec, mask_txt)
+        if spec[0] == "task":
+            feat = E.TaskRowFn.apply(self.arena().anchor, self.emb_task, spec[1])          # (1, H)
+            if mask_txt.dim() > 1:
+                feat = feat.unsqueeze(0).expand(mask_txt.shape[0], -1, -1)
+        else:
+            feat = self._embed_prompt(spec[1][0], mask_txt.device)                         # (1 or n, Lp, H)
+            if mask_txt.dim() > 1 and feat.shape[0] == 1:
+                feat = feat.expand(mask_txt.shape[0], -1, -1)
+            elif mask_txt.dim() == 1:
+                feat = feat[0]
+        return ids, m, feat
+
     def prepro_txt_inputs(self, txt, mask_txt, feat_txt, task_name=None, prompt=None):
-        """model.py:292-307 with enable_task_token / enable_prompt off (the shipped pretrain config): identity."""
-        if getattr(self.args, "enable_task_token", False) or (prompt is not None and getattr(self.args, "enable_prompt", False)):
-            raise NotImplementedError("task tokens / prompts are outside the built paths")
-        return txt, mask_txt, feat_txt
+        """model.py:292-307: the pre-text prepended to txt, mask_txt and feat_txt (identity with both switches off).  When feat_txt came from
+        go_feat with the same task_name / prompt it already holds the pre-text rows (one buffer, no copy); other features take one copy."""
+        spec = self._pretxt_spec(task_name, prompt)
+        if spec is None:
+            return txt, mask_txt, feat_txt
+        ids, m = self._pretxt_ids(spec, mask_txt)
+        done = getattr(feat_txt, "_lav_pretxt", None)
+        if done is not None and done[0] == spec[0] and (done[1] == spec[1] if spec[0] == "task" else done[1] is spec[1]):
+            out_feat = feat_txt
+        else:
+            _, _, pf = self.get_pretxt(mask_txt, task_name, prompt)
+            out_feat = torch.cat([pf.to(feat_txt.dtype), feat_txt], dim=-2)
+        return torch.cat([ids.to(txt.dtype), txt], dim=-1), torch.cat([m, mask_txt], dim=-1), out_feat
 
     # ---- checkpoint contract (model.py:352-429) ----------------------------------------------------
     def load_ckpt(self, ckpt):

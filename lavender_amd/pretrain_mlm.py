@@ -65,7 +65,10 @@ class LAVENDER_Pretrain_MLM(LAVENDER_Base):
     def forward(self, batch):
         """main_pretrain_mlm.py:55-119.  Same outputs; the B*O python loop of slices + T.cat is replaced by an
         index list (same numpy RNG draws) consumed by one gather kernel."""
+        pretxt = self._pretxt_spec("vtm", (batch or {}).get("vtm_prompt"))
         if fp32_validation(self.args):
+            if pretxt is not None:
+                raise NotImplementedError("the fp32 validation mode has no task token / prompt path")
             # tier-T2 validation mode (north_star "MLM logits within 1e-3 of reference"): fp32 activations end to end,
             # forward only, eval arithmetic -- lavender_amd/validate.py
             if self.training:
@@ -74,6 +77,8 @@ class LAVENDER_Pretrain_MLM(LAVENDER_Base):
             with torch.no_grad():
                 return validate.pretrain_mlm_forward(self, batch)
         batch = defaultdict(lambda: None, batch)
+        if pretxt is not None:
+            return self._forward_pretxt(batch, pretxt)
         img, txt, mask = [batch[key] for key in ["img", "txt", "mask"]]
         vt_mask, ans_mtm = batch["vt_mask"], batch["ans_mtm"]
         (_B, _T, _, _H, _W), (_, _X) = img.shape, txt.shape
@@ -117,6 +122,42 @@ class LAVENDER_Pretrain_MLM(LAVENDER_Base):
             ans_vtm[:, -1] = lab_vtm
             ans_vtm = ans_vtm.to(txt.device, non_blocking=True)
         return {"out_vtm": out_vtm, "out_mtm": out_mtm, "ans_vtm": ans_vtm, "ans_mtm": ans_mtm}
+
+
+    def _forward_pretxt(self, batch, pretxt):
+        """main_pretrain_mlm.py:65-119 with the "vtm" task token / batch["vtm_prompt"]: the MTM pass on the plain text, the VTM pass on
+        [pre-text ; text] (model.py:292-307 per pair).  The sequences differ in length, so the two passes run apart (the LAV_MERGE_PASSES=0
+        form).  The text is embedded ONCE, behind its pre-text in the one buffer with the video rows (both passes see the same text rows and
+        dropout, as in the reference); the MTM pass reads the text rows of that buffer and takes one copy of them."""
+        img, txt, mask = [batch[key] for key in ["img", "txt", "mask"]]
+        vt_mask, ans_mtm = batch["vt_mask"], batch["ans_mtm"]
+        (_B, _T, _, _H, _W), (_, _X) = img.shape, txt.shape
+        _h, _w = _H // self.patch_size, _W // self.patch_size
+        _O = min(_B, self.vtm_batch)
+        Lv = (1 + _h * _w) * _T
+        task_name, prompt = "vtm", batch["vtm_prompt"]
+        feat_img, mask_img, feat_pre, mask_txt = self.go_feat(img, txt, mask, vt_mask=vt_mask, task_name=task_name, prompt=prompt)
+        Lp = feat_pre.shape[1] - _X
+        txt_p, mask_p, feat_p = self.prepro_txt_inputs(txt, mask_txt, feat_pre, task_name=task_name, prompt=prompt)
+        out_m, _ = self.go_cross(feat_img, mask_img, feat_pre[:, Lp:], mask_txt)
+        vi, ti, tr = vtm_pairs(_B, _O)
+        lab_vtm = torch.where(torch.from_numpy(tr), self.true_token_id, self.false_token_id)
+        out_v, _ = self.go_cross_pairs(feat_img, mask_img, feat_p, mask_p, vi, ti)
+        L2 = Lv + Lp + _X
+        lab_cpu = batch["_ans_mtm_cpu"]
+        aware = self.training and bool(getattr(self.args, "loss_aware_head", False)) and lab_cpu is not None
+        rows_b, rows_x = (np.nonzero(lab_cpu.numpy() != -1) if aware else (None, None))
+        if aware and len(rows_b) > 0:
+            Hd = out_m.shape[-1]
+            out_mtm = self.fc_mtm(E.RowGatherFn.apply(out_m.reshape(-1, Hd), rows_b * (Lv + _X) + Lv + rows_x))
+            out_vtm = self.fc_mtm(E.RowGatherFn.apply(out_v.reshape(-1, Hd), np.arange(_B * _O) * L2 + L2 - 1))
+            return {"out_vtm": out_vtm, "out_mtm": out_mtm, "ans_vtm": lab_vtm.to(txt.device, non_blocking=True),
+                    "ans_mtm": lab_cpu[rows_b, rows_x].to(txt.device, non_blocking=True)}
+        out_mtm = self.fc_mtm(out_m[:, Lv:])
+        out_vtm = self.fc_mtm(out_v[:, Lv:])
+        ans_vtm = torch.full((_B * _O, Lp + _X), -1, dtype=torch.long)
+        ans_vtm[:, -1] = lab_vtm
+        return {"out_vtm": out_vtm, "out_mtm": out_mtm, "ans_vtm": ans_vtm.to(txt.device, non_blocking=True), "ans_mtm": ans_mtm}
 
 
 class Agent_Pretrain_MLM(Agent_Base):
@@ -186,6 +227,9 @@ class Agent_Pretrain_MLM(Agent_Base):
             batch = dict(batch)
             masked = self.masking(batch["txt"], batch["mask"])
             batch.update(masked)
+            if getattr(self.args, "enable_prompt", False):      # main_pretrain_mlm.py:217-219
+                batch["vtm_prompt"] = dl.dataset.get_vtm_prompt()
+                batch["cap_prompt"] = dl.dataset.get_cap_prompt()
             batch = self.prepare_batch(batch)
             r = self.step(batch, is_train)
             ret = {k: ret[k] + [l] for k, l in r.items()}

@@ -11,12 +11,13 @@
 
 The first two run one (video, text) sequence per sample through go_feat -> go_cross -> fc_mtm over the text positions -- the same HIP
 kernels as the pre-training path ("they inherit the speed-up because they sit on the same modules").
-Task tokens / prompts (enable_task_token / enable_prompt) are outside the built paths and raise in the base class."""
+With args.enable_task_token (batch["task_name"]) or args.enable_prompt (batch["prompt"] = (ids, mask)) the pre-text sits between the video
+and the text rows (LAVENDER_Base.go_feat / prepro_txt_inputs); as in the reference these callers label it -1 (prepro_pretxt)."""
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .agent import Agent_Base
+from .agent import Agent_Base, set_pretxt
 from .bert import BertConfigLite, BertOnlyMLMHead, load_hf_into, load_hf_state
 from .model import LAVENDER_Base
 
@@ -39,11 +40,16 @@ class LAVENDER_QAOE_MLM(LAVENDER_Base):
         img, txt, mask, ans = [batch.get(key) for key in ["img", "txt", "mask", "mask_ans"]]
         (_B, _T, _, _H, _W) = img.shape
         _h, _w = _H // 32, _W // 32
-        feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img, txt, mask)
-        ans, mask_txt, feat_txt = self.prepro_txt_inputs(ans, mask_txt, feat_txt, task_name=batch.get("task_name"), prompt=batch.get("prompt"))
+        task_name, prompt = batch.get("task_name"), batch.get("prompt")
+        feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img, txt, mask, task_name=task_name, prompt=prompt)
+        ans, mask_txt, feat_txt = self.prepro_txt_inputs(ans, mask_txt, feat_txt, task_name=task_name, prompt=prompt)
         out, _ = self.go_cross(feat_img, mask_img, feat_txt, mask_txt)
         out = self.fc_mtm(out[:, (1 + _h * _w) * _T:])
         return out, ans
+
+    def prepro_pretxt(self, task_or_prompt_txt):
+        """main_qaoe_mlm_lsmdc_fib.py:76-77 (main_qamc_mlm.py:121-122, main_retmc_mlm.py:87-88): the pre-text positions carry no label"""
+        return torch.ones_like(task_or_prompt_txt) * -1
 
 
 class LAVENDER_QAMC_MLM(LAVENDER_QAOE_MLM):
@@ -57,9 +63,10 @@ class LAVENDER_RetMC_MLM(LAVENDER_QAOE_MLM):
         img, txt, mask, ans = [batch.get(key) for key in ["img", "txt", "mask", "mask_ans"]]
         (_B, _T, _, _H, _W), (_, _O, _X) = img.shape, txt.shape
         _h, _w = _H // 32, _W // 32
-        feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img, txt.flatten(0, 1), mask.flatten(0, 1))
+        task_name, prompt = batch.get("task_name"), batch.get("prompt")
+        feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img, txt.flatten(0, 1), mask.flatten(0, 1), task_name=task_name, prompt=prompt)
         ans = ans.flatten(0, 1)
-        ans, mask_txt, feat_txt = self.prepro_txt_inputs(ans, mask_txt, feat_txt, task_name=batch.get("task_name"), prompt=batch.get("prompt"))
+        ans, mask_txt, feat_txt = self.prepro_txt_inputs(ans, mask_txt, feat_txt, task_name=task_name, prompt=prompt)
         vi, ti = np.repeat(np.arange(_B), _O), np.arange(_B * _O)       # video i with each of its O texts (expand + flatten, :100-103)
         out, _ = self.go_cross_pairs(feat_img, mask_img, feat_txt, mask_txt, vi, ti)
         out = self.fc_mtm(out[:, (1 + _h * _w) * _T:])
@@ -98,10 +105,12 @@ class Agent_RetMC_MLM(Agent_Base):
         return (out_mtm == ans_idx).float().tolist()
 
     def go_dl(self, ep, dl, is_train):
+        """main_retmc_mlm.py:145-170."""
         self._set_mode(is_train)
         ret = []
         for batch in dl:
-            r = self.step(self.prepare_batch(dict(batch)), is_train)
+            batch = set_pretxt(self.args, dict(batch), dl, "vtm" if ep == 0 else getattr(self.args, "task_token", "vtm"))
+            r = self.step(self.prepare_batch(batch), is_train)
             ret.extend(r) if isinstance(r, list) else ret.append(r)
         return self.reduce_mean(float(np.average(ret)))
 
@@ -145,7 +154,7 @@ class Agent_QAOE_MLM(Agent_Base):
         self._set_mode(is_train)
         ret = {}
         for batch in dl:
-            r = self.step(self.prepare_batch(dict(batch)), is_train)
+            r = self.step(self.prepare_batch(set_pretxt(self.args, dict(batch), dl, "oe")), is_train)
             for k, l in r.items():
                 ret.setdefault(k, []).extend(l if isinstance(l, list) else [l])
         return {k: self.reduce_mean(float(np.average(v))) for k, v in ret.items()}
@@ -184,6 +193,7 @@ class Agent_QAMC_MLM(Agent_Base):
         self._set_mode(is_train)
         ret = []
         for batch in dl:
-            r = self.step(self.prepare_batch(dict(batch)), is_train)
+            batch = set_pretxt(self.args, dict(batch), dl, "vtm" if ep == 0 else getattr(self.args, "task_token", "vtm"))
+            r = self.step(self.prepare_batch(batch), is_train)
             ret.extend(r) if isinstance(r, list) else ret.append(r)
         return self.reduce_mean(float(np.average(ret)))

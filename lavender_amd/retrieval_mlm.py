@@ -6,7 +6,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .agent import Agent_Base
+from .agent import Agent_Base, set_pretxt
 from .bert import BertConfigLite, BertOnlyMLMHead, load_hf_into, load_hf_state
 from .model import LAVENDER_Base
 
@@ -33,13 +33,14 @@ class LAVENDER_Retrieval_MLM(LAVENDER_Base):
         """main_retrieval_mlm.py:50-91: same (B*B, X, vocab) logits and (B*B, X) labels; the B^2 python list of
         slices + T.cat is one gather kernel over the pair index list."""
         img, txt, mask, vid = [batch.get(key) for key in ["img", "txt", "mask", "vid"]]
+        task_name, prompt = batch.get("task_name"), batch.get("prompt")
         (_B, _T, _, _H, _W) = img.shape
         _h, _w = _H // 32, _W // 32
-        _X = txt.shape[1]
         Lv = (1 + _h * _w) * _T
-        feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img, txt, mask)
-        if batch.get("task_name") is not None or batch.get("prompt") is not None:
-            self.prepro_txt_inputs(txt[0], mask_txt[0], feat_txt[0], task_name=batch.get("task_name"), prompt=batch.get("prompt"))
+        feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img, txt, mask, task_name=task_name, prompt=prompt)
+        # the pre-text (if any) is the same for every pair of text j: prepended once per text, not per pair as in the loop of :62-80
+        txt, mask_txt, feat_txt = self.prepro_txt_inputs(txt, mask_txt, feat_txt, task_name=task_name, prompt=prompt)
+        _X = txt.shape[1]
         vi, ti = all_pairs(_B)
         out, _ = self.go_cross_pairs(feat_img, mask_img, feat_txt, mask_txt, vi, ti)
         out = self.fc_mtm(out[:, Lv:])
@@ -61,9 +62,10 @@ class Agent_Retrieval_MLM(Agent_Base):
         with torch.set_grad_enabled(is_train):
             out, ans = self.forward_step(batch)
             if is_train:
+                n_pairs = out.shape[0]                         # one labelled position per pair
                 out = out.flatten(0, len(out.shape) - 2)
                 ans = ans.flatten(0, len(ans.shape) - 1)
-                ls = self.loss_func(out, ans, out.shape[0] // batch["txt"].shape[1])
+                ls = self.loss_func(out, ans, n_pairs)
                 self.backward_step(ls)
                 return ls.item() if sync else ls.detach()
         _B = len(batch["vid"])
@@ -81,7 +83,7 @@ class Agent_Retrieval_MLM(Agent_Base):
         self._set_mode(is_train)
         ret = []
         for batch in dl:
-            batch = self.prepare_batch(dict(batch))
+            batch = self.prepare_batch(set_pretxt(self.args, dict(batch), dl, "vtm"))
             r = self.step(batch, is_train)
             ret.extend(r) if isinstance(r, list) else ret.append(r)
         return self.reduce_mean(float(np.average(ret)))
@@ -96,8 +98,11 @@ class LAVENDER_RetrievalMlmEval(LAVENDER_Retrieval_MLM):
         from . import hip as K
         if typ == 'feat':
             img, txt, mask = [batch.get(key) for key in ["img", "txt", "mask"]]
+            task_name = batch.get("task_name")
+            # eval_retrieval_mlm.py:24,154-164: the prompt comes as (n, Lp) rows prompt_txt / prompt_mask (a block per text)
+            prompt = (batch["prompt_txt"], batch["prompt_mask"]) if batch.get("prompt_txt") is not None else None
             _B, _Clips, _T, _C, _H, _W = img.shape
-            feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img.view(-1, _T, _C, _H, _W), txt, mask)
+            feat_img, mask_img, feat_txt, mask_txt = self.go_feat(img.view(-1, _T, _C, _H, _W), txt, mask, task_name=task_name, prompt=prompt)
             Lv, Hd = feat_img.shape[1], feat_img.shape[2]
             if _Clips > 1:                                # mean over the clips of a video: gather-sum kernel + 1/Clips scale kernel
                 rows = feat_img.reshape(_B * _Clips * Lv, Hd)
@@ -113,8 +118,7 @@ class LAVENDER_RetrievalMlmEval(LAVENDER_Retrieval_MLM):
             else:
                 feat_img = feat_img.view(_B, Lv, Hd)
             mask_img = mask_img.view(_B, _Clips, -1)[:, 0, :]
-            txt, mask_txt, feat_txt = self.prepro_txt_inputs(txt, mask_txt, feat_txt, task_name=batch.get("task_name"),
-                                                             prompt=None)
+            txt, mask_txt, feat_txt = self.prepro_txt_inputs(txt, mask_txt, feat_txt, task_name=task_name, prompt=prompt)
             return feat_img, mask_img, feat_txt, mask_txt, txt
         elif typ == 'cross':
             feat_img, mask_img, feat_txt, mask_txt = [batch.get(key) for key in ["feat_img", "mask_img", "feat_txt", "mask_txt"]]
