@@ -3,12 +3,19 @@
 MLM head; forward + backward + clip + AdamW) on N MI355X GPUs of one node, data parallel.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one synthetic batch of 32 clips per GPU (inputs resident in HBM, labels
-already built).  Rank 0 prints ONE JSON line (contract in the task statement): `value` = whole-job samples/s,
-`roofline` = the dominant kernel (the bf16 MFMA GEMM) measured per launch with HIP events on its stream,
-`cpu_baseline` = the CPU oracle (restated reference path) timed on this box's host cores at N=1.
+already built).  Rank 0 prints ONE JSON line: `value` = whole-job samples/s over the --steps timed steps, `ms_per_step`
+= wall-clock milliseconds per timed step.
+
+A plain run does only that: set up, warm up, time the steps, write --dump-outputs, print the line.  --full adds the
+measurements beyond the headline, each after the timed steps and outside their window:
+`ms_per_step_reference_loop` (the reference's own loop semantics), `roofline` (the dominant kernel, the bf16 MFMA GEMM,
+measured per launch with HIP events on its stream over two more steps), `cpu_baseline` (the CPU oracle, a restated
+reference path, timed on the host cores at N=1), `side_workloads` (cfg4, cfg5) and `ab_baseline` / `dp1_*` (child runs
+of this script).  In a plain line `ms_per_step_reference_loop` and `roofline` are null.
 """
 import argparse
 import json
@@ -152,10 +159,10 @@ AB_ENV = {"LAV_FIRST_TOUCH": "0", "LAV_FUSION_SRC": "0", "LAV_GEMM_PS": "0"}    
 
 
 def child_ms(extra_args=(), env=None, steps=10, warmup=3, timeout_s=150):
-    """ms per cfg2 step of a child process of this script (no CPU leg, no side workloads, no reference loop)."""
+    """ms per cfg2 step of a plain child run of this script (no --full: no CPU leg, no side workloads, no reference loop, no roofline)."""
     import subprocess
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-ref-loop",
-                        "--no-side-workloads", *extra_args], capture_output=True, text=True, timeout=timeout_s, env={**os.environ, **(env or {})})
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), *extra_args],
+                       capture_output=True, text=True, timeout=timeout_s, env={**os.environ, **(env or {})})
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     if not lines:
         raise RuntimeError(f"child {list(extra_args)} {env or {}} printed no line (rc {p.returncode}): {p.stderr.strip()[-300:]}")
@@ -186,13 +193,13 @@ def ab_and_dp_legs():
 
 
 def side_workloads():
-    """cfg4 (Swin-L 384^2, B = 8) and cfg5 (retrieval, 8 x 8 pairs) for 5 timed steps each, in child processes AFTER the contract line's
-    measurement (outside its timed region; the parent is idle meanwhile): the driver's record then carries them too.  Not the headline metric."""
+    """cfg4 (Swin-L 384^2, B = 8) and cfg5 (retrieval, 8 x 8 pairs) for 5 timed steps each, in plain child runs AFTER the contract line's
+    measurement (outside its timed region; the parent is idle meanwhile): the --full record then carries them too.  Not the headline metric."""
     import subprocess
     res = {}
     for wl in ("cfg4", "cfg5"):
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-ref-loop"],
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "5", "--warmup", "2"],
                                capture_output=True, text=True, timeout=180)
             line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
             d = json.loads(line)
@@ -201,6 +208,22 @@ def side_workloads():
         except Exception as e:  # a side measurement must never take the contract line down
             res[wl] = {"error": f"{type(e).__name__}: {e}"[:200]}
     return res
+
+
+def full_legs(a, world):
+    """The measurements a run makes beyond its headline (set-up, warm-up, timed steps, --dump-outputs, the result line), in the
+    order they run after the timed steps.  None of them without --full; the --no-* switches drop single legs of a --full run."""
+    if not a.full:
+        return []
+    legs = []
+    if a.workload != "cfg5" and a.input == "resident" and not a.no_ref_loop:
+        legs.append("ref_loop")
+    legs.append("roofline")
+    if world == 1 and a.workload == "cfg2" and not a.no_cpu_baseline:
+        legs.append("cpu_baseline")
+        if not a.no_side_workloads and a.input == "resident":
+            legs.append("children")      # side workloads, A/B and 1-rank RCCL child runs
+    return legs
 
 
 DUMP_PARAM_SAMPLE = 1 << 22       # 16 MB of fp32: the full parameter set of cfg2 is 0.9 GB
@@ -223,7 +246,7 @@ def dump_outputs(d, model, agent, last, rank):
     del flat
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -239,9 +262,12 @@ def main():
     ap.add_argument("--loss-aware-head", action="store_true",
                     help="opt-in side measurement (NOT the contract line): MLM head + loss on the supervised positions only")
     ap.add_argument("--layers", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-workloads", action="store_true", help="skip the cfg4 / cfg5 side measurements appended to the default cfg2 line")
-    ap.add_argument("--no-ref-loop", action="store_true", help="skip the ms_per_step_reference_loop leg (profile collection: keeps the step count of the run fixed)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the reference-loop timing, the GEMM roofline "
+                         "(two more steps), the CPU baseline, the cfg4 / cfg5 side workloads and the A/B and 1-rank RCCL child runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and with it the side workloads and child runs)")
+    ap.add_argument("--no-side-workloads", action="store_true", help="with --full: skip the cfg4 / cfg5 side measurements and the A/B and 1-rank RCCL child runs")
+    ap.add_argument("--no-ref-loop", action="store_true", help="with --full: skip the ms_per_step_reference_loop leg (profile collection: keeps the step count of the run fixed)")
     ap.add_argument("--force-dp", action="store_true",
                     help="side measurement at --gpus 1: join a 1-rank RCCL process group and attach the gradient reducer (what the "
                          "overlap bookkeeping and the comm-stream events cost when there is nobody to talk to)")
@@ -254,6 +280,11 @@ def main():
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32): the losses "
                          "and a fixed, seeded sample of the updated fp32 parameters -- for comparing two builds on the same inputs")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
+    return ap
+
+
+def main():
+    ap = arg_parser()
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
@@ -278,6 +309,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", 1))
     if world != a.gpus:
         raise SystemExit(f"bench.py: launched with WORLD_SIZE={world} but --gpus {a.gpus}: refusing to report a {world}-rank run as {a.gpus} GPUs")
+    legs = full_legs(a, world)
     import torch.distributed as dist
     use_cuda = torch.cuda.is_available()
     if use_cuda:
@@ -411,7 +443,7 @@ def main():
     # step a HOST batch (pinned, as a DataLoader with pin_memory hands it over), masking() on the host, prepare_batch (H2D of frames,
     # ids, labels) and .item() on both losses -- i.e. one device round trip per step and no enqueue run-ahead
     ref_loop_ms = None
-    if not retrieval and feed is None and use_cuda and not a.no_ref_loop:
+    if "ref_loop" in legs and use_cuda:
         host_batches = []
         for i in range(nb):
             hb = synth_batch(B, T, S, X, rank * 7 + i, "cpu")
@@ -439,76 +471,77 @@ def main():
     # ---- dominant-kernel roofline: every K-contiguous (layout 0) GEMM launch of one more step, HIP events on its stream ----
     # every rank runs the sampling step (it contains the gradient all-reduce); only rank 0 instruments and reports
     roof = None
-    rec = []
-    orig = K.gemm
+    if "roofline" in legs:
+        rec = []
+        orig = K.gemm
 
-    def timed(layout, A, Bm, M, N, Kd, **kw):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = orig(layout, A, Bm, M, N, Kd, **kw)
-        e1.record()
-        # algorithmic HBM bytes of the launch: operands once, output once, plus the epilogue tensors it reads / writes
-        by = 2.0 * (M * Kd + N * Kd + M * N)
-        for k in ("preact", "gelu_in", "residual"):
-            if kw.get(k) is not None:
-                by += 2.0 * M * N
-        rec.append((layout, 2.0 * M * N * Kd, e0, e1, by))
-        return r
-    # the stage-level C entries (engine.STAGE_C) enqueue their GEMMs from C, where this Python hook does not see them: the two sampling
-    # steps run the per-kernel host path instead -- the same kernels with the same arguments (bit-identical, tests/test_gpu_variants.py),
-    # each launch bracketed by its own pair of HIP events on the launch stream
-    import lavender_amd.engine as _E
-    _stage_c = _E.STAGE_C
-    _E.STAGE_C = False
-    if rank == 0:
-        K.gemm = timed
-    run_step(0)
-    torch.cuda.synchronize()
-    rec_shared = rec
-    # the same sampling once more with the weight-gradient side stream off: the timed steps overlap dW kernels with the
-    # chain, so the per-launch durations above include sharing the CUs; this pass times each GEMM launch on its own
-    rec = []
-    _side = _E._DW_SIDE
-    _E._DW_SIDE = False
-    run_step(0)
-    torch.cuda.synchronize()
-    _E._DW_SIDE = _side
-    _E.STAGE_C = _stage_c
-    rec_iso, rec = rec, rec_shared
-    K.gemm = orig
-    if rank == 0:
-        by = {}
-        for layout, fl, e0, e1, nbytes in rec:
-            d = by.setdefault(layout, [0, 0.0, 0.0, 0.0])
-            d[0] += 1; d[1] += fl; d[2] += e0.elapsed_time(e1) * 1e-3; d[3] += nbytes
-        n, fl, tm, nb = by[0]
-        # HBM bytes per launch from the committed rocprofv3 PMC passes of this same command (profiles/)
-        traffic = None
-        try:
-            with open(os.path.join(ROOT, "profiles", TRAFFIC_FILE + ".json")) as fh:
-                pm = json.load(fh)
-            if a.workload == "cfg2" and B == 32 and a.layers == 12 and a.size == "base":
-                traffic = pm["hbm_bytes_per_launch"]
-        except Exception:
+        def timed(layout, A, Bm, M, N, Kd, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = orig(layout, A, Bm, M, N, Kd, **kw)
+            e1.record()
+            # algorithmic HBM bytes of the launch: operands once, output once, plus the epilogue tensors it reads / writes
+            by = 2.0 * (M * Kd + N * Kd + M * N)
+            for k in ("preact", "gelu_in", "residual"):
+                if kw.get(k) is not None:
+                    by += 2.0 * M * N
+            rec.append((layout, 2.0 * M * N * Kd, e0, e1, by))
+            return r
+        # the stage-level C entries (engine.STAGE_C) enqueue their GEMMs from C, where this Python hook does not see them: the two sampling
+        # steps run the per-kernel host path instead -- the same kernels with the same arguments (bit-identical, tests/test_gpu_variants.py),
+        # each launch bracketed by its own pair of HIP events on the launch stream
+        import lavender_amd.engine as _E
+        _stage_c = _E.STAGE_C
+        _E.STAGE_C = False
+        if rank == 0:
+            K.gemm = timed
+        run_step(0)
+        torch.cuda.synchronize()
+        rec_shared = rec
+        # the same sampling once more with the weight-gradient side stream off: the timed steps overlap dW kernels with the
+        # chain, so the per-launch durations above include sharing the CUs; this pass times each GEMM launch on its own
+        rec = []
+        _side = _E._DW_SIDE
+        _E._DW_SIDE = False
+        run_step(0)
+        torch.cuda.synchronize()
+        _E._DW_SIDE = _side
+        _E.STAGE_C = _stage_c
+        rec_iso, rec = rec, rec_shared
+        K.gemm = orig
+        if rank == 0:
+            by = {}
+            for layout, fl, e0, e1, nbytes in rec:
+                d = by.setdefault(layout, [0, 0.0, 0.0, 0.0])
+                d[0] += 1; d[1] += fl; d[2] += e0.elapsed_time(e1) * 1e-3; d[3] += nbytes
+            n, fl, tm, nb = by[0]
+            # HBM bytes per launch from the committed rocprofv3 PMC passes of this same command (profiles/)
             traffic = None
-        tot_fl = sum(v[1] for v in by.values()); tot_t = sum(v[2] for v in by.values())
-        iso = [0, 0.0, 0.0]
-        for lay_i, fl_i, e0_i, e1_i, _nb_i in rec_iso:
-            if lay_i == 0:
-                iso[0] += 1; iso[1] += fl_i; iso[2] += e0_i.elapsed_time(e1_i) * 1e-3
-        roof = {"bound": "mfma", "kernel": "lav_gemm_bf16 layout 0 (forward x.W^T and input-gradient dy.(W^T)^T GEMMs: gemm_ps<256 | 192 rows> / gemm_huge / gemm_big / gemm_kernel<NT>)",
-                "achieved": round(fl / tm / 1e12, 2),
-                "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(fl / tm / 1e12 / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
-                "traffic_unit": f"HBM bytes per launch, STATIC: read from the committed rocprofv3 PMC passes of this same command (FETCH_SIZE x2 + WRITE_SIZE, profiles/{TRAFFIC_FILE}.md), not collected in this run",
-                "algorithmic_bytes_per_launch": round(nb / n),
-                "launches_per_step": n, "avg_launch_us": round(tm / n * 1e6, 2), "avg_launch_gflop": round(fl / n / 1e9, 3),
-                "note": "achieved / avg_launch_us are measured in the shipped configuration, where weight-gradient GEMMs of a second "
-                        "stream share the CUs with these launches; `isolated` = same launches with that stream off; the sampling steps issue "
-                        "every launch through the per-kernel host path (the stage-level C entries enqueue the identical launches from C)",
-                "isolated": {"achieved": round(iso[1] / iso[2] / 1e12, 2), "frac": round(iso[1] / iso[2] / 1e12 / PEAK_BF16_TFLOPS, 4),
-                             "avg_launch_us": round(iso[2] / max(iso[0], 1) * 1e6, 2)},
-                "all_gemm_layouts": {"launches": sum(v[0] for v in by.values()), "tflops": round(tot_fl / tot_t / 1e12, 2),
-                                     "gemm_time_ms_per_step": round(tot_t * 1e3, 2)}}
+            try:
+                with open(os.path.join(ROOT, "profiles", TRAFFIC_FILE + ".json")) as fh:
+                    pm = json.load(fh)
+                if a.workload == "cfg2" and B == 32 and a.layers == 12 and a.size == "base":
+                    traffic = pm["hbm_bytes_per_launch"]
+            except Exception:
+                traffic = None
+            tot_fl = sum(v[1] for v in by.values()); tot_t = sum(v[2] for v in by.values())
+            iso = [0, 0.0, 0.0]
+            for lay_i, fl_i, e0_i, e1_i, _nb_i in rec_iso:
+                if lay_i == 0:
+                    iso[0] += 1; iso[1] += fl_i; iso[2] += e0_i.elapsed_time(e1_i) * 1e-3
+            roof = {"bound": "mfma", "kernel": "lav_gemm_bf16 layout 0 (forward x.W^T and input-gradient dy.(W^T)^T GEMMs: gemm_ps<256 | 192 rows> / gemm_huge / gemm_big / gemm_kernel<NT>)",
+                    "achieved": round(fl / tm / 1e12, 2),
+                    "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(fl / tm / 1e12 / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
+                    "traffic_unit": f"HBM bytes per launch, STATIC: read from the committed rocprofv3 PMC passes of this same command (FETCH_SIZE x2 + WRITE_SIZE, profiles/{TRAFFIC_FILE}.md), not collected in this run",
+                    "algorithmic_bytes_per_launch": round(nb / n),
+                    "launches_per_step": n, "avg_launch_us": round(tm / n * 1e6, 2), "avg_launch_gflop": round(fl / n / 1e9, 3),
+                    "note": "achieved / avg_launch_us are measured in the shipped configuration, where weight-gradient GEMMs of a second "
+                            "stream share the CUs with these launches; `isolated` = same launches with that stream off; the sampling steps issue "
+                            "every launch through the per-kernel host path (the stage-level C entries enqueue the identical launches from C)",
+                    "isolated": {"achieved": round(iso[1] / iso[2] / 1e12, 2), "frac": round(iso[1] / iso[2] / 1e12 / PEAK_BF16_TFLOPS, 4),
+                                 "avg_launch_us": round(iso[2] / max(iso[0], 1) * 1e6, 2)},
+                    "all_gemm_layouts": {"launches": sum(v[0] for v in by.values()), "tflops": round(tot_fl / tot_t / 1e12, 2),
+                                         "gemm_time_ms_per_step": round(tot_t * 1e3, 2)}}
     if world > 1:
         dist.barrier()
 
@@ -547,9 +580,9 @@ def main():
                           "step_mfma_frac": round(value / world * fstep / 1e12 / PEAK_BF16_TFLOPS, 4),
                           "loss": loss_vals},
                "roofline": roof}
-        if world == 1 and not a.no_cpu_baseline and a.workload == "cfg2":
+        if "cpu_baseline" in legs:
             out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and a.workload == "cfg2" and not a.no_side_workloads and not a.no_cpu_baseline and a.input == "resident":
+        if "children" in legs:
             # the children need the HBM this process's caching allocator still holds (a child that finds the device full dies in the HSA runtime)
             import gc
             gc.collect(); torch.cuda.synchronize(); torch.cuda.empty_cache()

@@ -258,6 +258,27 @@ def test_bench_dump_outputs_writes_the_same_float_arrays_for_the_same_state(tmp_
     assert not os.path.exists(tmp_path / "rank1")
 
 
+def test_bench_plain_run_measures_only_the_headline():
+    """A plain bench.py run stops at its result line: the reference loop, the roofline sampling steps, the CPU baseline and the
+    child runs (side workloads, A/B, 1-rank RCCL) come with --full only, where the --no-* switches drop single legs as before."""
+    import bench
+
+    def legs(*argv, world=1):
+        return bench.full_legs(bench.arg_parser().parse_args(list(argv)), world)
+    everything = ["ref_loop", "roofline", "cpu_baseline", "children"]
+    for argv in ([], ["--gpus", "1", "--steps", "20", "--warmup", "5"], ["--workload", "cfg4"], ["--input", "tsv"], ["--force-dp"],
+                 ["--dump-outputs", "d"]):
+        assert legs(*argv) == [] and legs(*argv, world=8) == [], argv
+    assert legs("--full") == everything
+    assert legs("--full", world=8) == ["ref_loop", "roofline"]
+    assert legs("--full", "--no-ref-loop") == everything[1:]
+    assert legs("--full", "--no-cpu-baseline") == ["ref_loop", "roofline"]
+    assert legs("--full", "--no-side-workloads") == everything[:3]
+    assert legs("--full", "--workload", "cfg4") == ["ref_loop", "roofline"]
+    assert legs("--full", "--workload", "cfg5") == ["roofline"]
+    assert legs("--full", "--input", "tsv") == ["roofline", "cpu_baseline"]
+
+
 def test_hf_checkpoint_loader_renames_legacy_layernorm_keys_and_ties_the_decoder(tmp_path):
     """Stock bert-base-uncased files name LayerNorm parameters gamma / beta and omit the tied cls.predictions.decoder.weight;
     `from_pretrained` (model.py:100-102, main_pretrain_mlm.py:46-48) fixes both up, so must load_hf_state."""

@@ -3,6 +3,6 @@
 VAR=$1; A=$2; B=$3; N=${4:-2}
 for i in $(seq $N); do
   for v in $A $B; do
-    env $VAR=$v python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-ref-loop 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$VAR=$v', d['ms_per_step'], d.get('ms_per_step_median'), d['roofline']['frac'])"
+    env $VAR=$v python bench.py --steps 30 --warmup 8 --full --no-cpu-baseline --no-ref-loop 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$VAR=$v', d['ms_per_step'], d.get('ms_per_step_median'), d['roofline']['frac'])"
   done
 done

@@ -17,7 +17,7 @@ bash tools/sq_one.sh win win_ python tools/win_bias_one.py > $D/sq_win.log 2>&1;
 python tools/seq_probe.py > $D/${R}_seq_probe.txt 2>&1
 python tools/win_probe.py > $D/${R}_win_probe.txt 2>&1
 python tools/convergence_run.py 400 > $D/${R}_convergence_cfg2.txt 2>&1
-python bench.py > $D/${R}_bench_default.json 2> $D/bench.err
+python bench.py --full > $D/${R}_bench_default.json 2> $D/bench.err
 tail -c 600 $D/${R}_bench_default.json
 # gpurun merges at most 64 MiB back: the rocpd databases stay on the box
 rm -rf gpurun_out/prof_${R} gpurun_out/prof_${R}_cfg4 gpurun_out/prof_${R}_cfg5 gpurun_out/sq_seq gpurun_out/sq_win

@@ -45,7 +45,7 @@ if len(sys.argv) > 5:
     wb = sum(w.get(k, (0, 0, 0))[1] for k in fam) * 1024 / n
     allf = sum(v[1] for v in f.values()) * 2 * 1024
     allw = sum(v[1] for v in w.values()) * 1024
-    json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline",
+    json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-ref-loop",
                "kernel": "layout-0 GEMMs (gemm_ps/gemm_huge/h192/big/gemm_kernel<true,true,*>): forward x.W^T and input-gradient dy.(W^T)^T",
                "launches": n, "launches_per_step": n // steps, "fetch_bytes_per_launch": int(fb), "write_bytes_per_launch": int(wb),
                "hbm_bytes_per_launch": int(fb + wb), "step_fetch_GB": round(allf / steps / 1e9, 1), "step_write_GB": round(allw / steps / 1e9, 1),
