@@ -50,7 +50,7 @@ const char* lav_last_error(void);
 #define LAV_WS_LN_DEFER 2
 size_t lav_workspace_bytes(int kind);
 int lav_set_workspace(void* stream, int kind, void* ptr, size_t bytes);
-int lav_abi_version(void);   /* 7: lav_text_embed_pre_fwd / lav_text_embed_pre_bwd (additive), lav_bert_layer_desc.ln2_eps, lav_pair_key_mask, lav_gemm_epilogue.assign / lav_gemm_tn_job.assign / lav_*_bwd_desc.assign_mask (first-touch weight gradients), lav_winl_select declared, lav_set_error no longer exported; 6: lav_workspace_bytes / lav_set_workspace, lav_layernorm_set_defer per stream + lav_layernorm_flush_all, lav_ln_bwd_extra.finish_stream removed, LAV_E_WORKSPACE; 5: lav_gemm_tn_grouped (+ lav_*_bwd_desc.group_splits), fp16 rows (out_mode 3, residual_f32 / x_f32 = 2, lav_bert_layer_desc.stream_f16), lav_layernorm_set_defer / lav_layernorm_flush, lav_attn_desc.bias_map / lav_attention_build_bias_map; 4: lav_gemm_epilogue.c_pad_writable; 3: a_rowmap / res_rowmap / res_ln_*; 2: residual_f32, lav_ln_f32, causal_from, lav_scale_by_scalar, lav_v_* validation entries, lavender_pipeline.h */
+int lav_abi_version(void);   /* 7: lav_attention_rows / lav_bert_layer_fwd_rows / lav_mlm_pair_readout / lav_retrieval_rank (additive), lav_text_embed_pre_fwd / lav_text_embed_pre_bwd (additive), lav_bert_layer_desc.ln2_eps, lav_pair_key_mask, lav_gemm_epilogue.assign / lav_gemm_tn_job.assign / lav_*_bwd_desc.assign_mask (first-touch weight gradients), lav_winl_select declared, lav_set_error no longer exported; 6: lav_workspace_bytes / lav_set_workspace, lav_layernorm_set_defer per stream + lav_layernorm_flush_all, lav_ln_bwd_extra.finish_stream removed, LAV_E_WORKSPACE; 5: lav_gemm_tn_grouped (+ lav_*_bwd_desc.group_splits), fp16 rows (out_mode 3, residual_f32 / x_f32 = 2, lav_bert_layer_desc.stream_f16), lav_layernorm_set_defer / lav_layernorm_flush, lav_attn_desc.bias_map / lav_attention_build_bias_map; 4: lav_gemm_epilogue.c_pad_writable; 3: a_rowmap / res_rowmap / res_ln_*; 2: residual_f32, lav_ln_f32, causal_from, lav_scale_by_scalar, lav_v_* validation entries, lavender_pipeline.h */
 
 /* ---------------------------------------------------------------------------------------------
  * GEMM with fused epilogue.  Replaces every nn.Linear on the path (video_swin.py:73-79,137-139,
@@ -670,6 +670,67 @@ typedef struct lav_beam_reparent_desc {
     void* dst_k[LAV_REPARENT_MAX_LAYERS]; void* dst_v[LAV_REPARENT_MAX_LAYERS];
 } lav_beam_reparent_desc;
 int lav_beam_reparent(void* stream, const lav_beam_reparent_desc* d);
+
+/* ---------------------------------------------------------------------------------------------
+ * Text-to-video retrieval evaluation (csrc/retrieval.hip, csrc/stages.cpp; eval_retrieval_mlm.py:138-247, eval only: no dropout, no atomics,
+ * two runs give identical bits).  Every (caption, video) pair runs the fusion encoder and the MLM head, and only the appended [MASK] row of
+ * the last layer and two vocabulary columns reach its score p_true / (p_true + p_false): the last layer runs everything after its QKV GEMM
+ * on that one row per pair, and the head reads out two decoder rows instead of the full vocabulary.  (ABI 7, additive.)
+ *
+ * lav_attention_rows: out[s] (bf16, row pitch ldo) = softmax(q_s K_s^T * scale + mask) V_s per head, where q_s is row q_row[s] of sequence s
+ * of the (n * L, ldq >= 3 * heads * 64) qkv rows of the full-width QKV GEMM and K_s / V_s are all L rows of that sequence; key_mask (n, L)
+ * int32 as lav_pair_key_mask builds it.  head_dim 64, L <= 4096, fp32 softmax.  A q_row outside [0, L) gives a zero row; a row whose keys are
+ * all masked gives a zero row. */
+int lav_attention_rows(void* stream, int n, int L, int heads, int head_dim, const void* qkv, long ldq, const int32_t* key_mask,
+                       const int32_t* q_row, float scale, void* out, long ldo);
+
+/* lav_bert_layer_fwd_rows: lav_bert_layer_fwd at eval with every step after the QKV GEMM restricted to the n_seq selected rows (row q_row[s] of
+ * sequence s):  qkv = x Wqkv^T + b over all n_seq * L rows (x read through x_rowmap when given: lav_gemm_epilogue.a_rowmap);
+ * cx = lav_attention_rows(qkv);  pre1 = res + cx Wao^T + b;  x1 = LN1(pre1);  h = gelu(x1 Wff1^T + b);  pre2 = x1 + h Wff2^T + b;  y = LN2(pre2).
+ * `res` row s is row res_rowmap[s] of the residual the layer would read in full: bf16 (res_dtype 0: the embeddings, or the un-expanded pair
+ * source), fp32 (1) or fp16 (2) rows, with res_mean / res_rstd / res_gamma / res_beta when those rows are the PRE-LayerNorm rows of the
+ * producing layer (lav_gemm_epilogue.res_ln_*).  pre1 / pre2 / y32 are fp32 (n_seq, hidden); mean* / rstd* are n_seq floats (mean2 / rstd2 may
+ * be NULL); every buffer is the caller's. */
+typedef struct lav_bert_layer_rows_desc {
+    int n_seq, L, hidden, heads, ffn;
+    float ln_eps, ln2_eps;                                 /* ln2_eps 0: the same as ln_eps */
+    const int32_t* key_mask;                               /* (n_seq, L) */
+    const int32_t* q_row;                                  /* (n_seq) */
+    const void* w_qkv; const float* b_qkv;
+    const void* w_ao; const float* b_ao; const float* ln1_gamma; const float* ln1_beta;
+    const void* w_ff1; const float* b_ff1;
+    const void* w_ff2; const float* b_ff2; const float* ln2_gamma; const float* ln2_beta;
+    const void* x; const int32_t* x_rowmap;                /* bf16 rows, (n_seq * L) of them or read through x_rowmap (int32 [n_seq * L]) */
+    const void* res; long ldr; int res_dtype; const int32_t* res_rowmap;   /* res_rowmap: int32 [n_seq], required */
+    const float* res_mean; const float* res_rstd; const float* res_gamma; const float* res_beta;   /* or all NULL */
+    void* qkv;                                             /* bf16 (n_seq * L, 3 hidden) */
+    void* cx; float* pre1; float* mean1; float* rstd1; void* x1; void* h; float* pre2; float* mean2; float* rstd2;
+    void* y; float* y32;                                   /* outputs: bf16 and fp32 (n_seq, hidden) */
+} lav_bert_layer_rows_desc;
+int lav_bert_layer_fwd_rows(void* stream, const lav_bert_layer_rows_desc* d);
+
+/* lav_mlm_pair_readout: the MLM head (BertOnlyMLMHead) on n rows, read out at two vocabulary entries.  t = gelu(x Wt^T + b) (fp32, the tile GEMM
+ * with the GELU epilogue, into the caller's (n, hidden) scratch), then per row in fp32: LayerNorm(t) (ln_eps), p_true / p_false = its dot products
+ * with rows true_id / false_id of the decoder weight + the tied bias, s = p_true / (p_true + p_false) (raw logits, no softmax).  s goes to
+ * scores[out_row[k] * ld_scores + out_col[k]] (entries outside score_rows x score_cols are skipped), (p_true, p_false) to logits (n, 2) when given. */
+typedef struct lav_mlm_pair_readout_desc {
+    int n, hidden, vocab, true_id, false_id;
+    float ln_eps;
+    const void* x; long ldx;                               /* bf16 (n, hidden) */
+    const void* w_dense; const float* b_dense;             /* transform dense (hidden, hidden) bf16 / fp32 */
+    const float* ln_gamma; const float* ln_beta;
+    const void* w_dec; long ldw_dec; const float* b_dec;   /* decoder weight (vocab, ldw_dec) bf16 and its (tied) bias */
+    float* t;                                              /* scratch fp32 (n, hidden) */
+    const int32_t* out_row; const int32_t* out_col;        /* (n) */
+    float* scores; long ld_scores; int score_rows, score_cols;
+    float* logits;                                         /* (n, 2) fp32 or NULL */
+} lav_mlm_pair_readout_desc;
+int lav_mlm_pair_readout(void* stream, const lav_mlm_pair_readout_desc* d);
+
+/* lav_retrieval_rank: out[t] = 1-based position of column gt[t] when the columns of row t of S (n_text, ldS) fp32 are sorted by score descending,
+ * stably in column order (eval_retrieval_mlm.py:223-227): 1 + #{v : S[t,v] > S[t,gt]} + #{v < gt : S[t,v] == S[t,gt]}.  NaN sorts after every
+ * number and NaNs keep their column order.  A gt outside [0, n_video) gives 0.  One workgroup per row. */
+int lav_retrieval_rank(void* stream, int n_text, int n_video, const float* S, long ldS, const int32_t* gt, int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
  * Process-wide probe switches: environment variables read ONCE by the library on first use (not part of the contract; every setting

@@ -126,6 +126,21 @@ class BeamReparentDesc(C.Structure):       # struct lav_beam_reparent_desc
                 [(n, vp * REPARENT_MAX_LAYERS) for n in ("src_k", "src_v", "dst_k", "dst_v")])
 
 
+
+class BertLayerRowsDesc(C.Structure):      # struct lav_bert_layer_rows_desc (retrieval pair scorer)
+    _fields_ = ([(n, i32) for n in ("n_seq", "L", "hidden", "heads", "ffn")] + [(n, f32) for n in ("ln_eps", "ln2_eps")] +
+                [(n, vp) for n in ("key_mask", "q_row", "w_qkv", "b_qkv", "w_ao", "b_ao", "ln1_gamma", "ln1_beta", "w_ff1", "b_ff1", "w_ff2", "b_ff2",
+                                   "ln2_gamma", "ln2_beta", "x", "x_rowmap", "res")] + [("ldr", i64), ("res_dtype", i32)] +
+                [(n, vp) for n in ("res_rowmap", "res_mean", "res_rstd", "res_gamma", "res_beta", "qkv", "cx", "pre1", "mean1", "rstd1", "x1", "h",
+                                   "pre2", "mean2", "rstd2", "y", "y32")])
+
+
+class MlmPairReadoutDesc(C.Structure):     # struct lav_mlm_pair_readout_desc
+    _fields_ = ([(n, i32) for n in ("n", "hidden", "vocab", "true_id", "false_id")] + [("ln_eps", f32), ("x", vp), ("ldx", i64)] +
+                [(n, vp) for n in ("w_dense", "b_dense", "ln_gamma", "ln_beta", "w_dec")] + [("ldw_dec", i64)] +
+                [(n, vp) for n in ("b_dec", "t", "out_row", "out_col", "scores")] + [("ld_scores", i64), ("score_rows", i32), ("score_cols", i32),
+                                                                                     ("logits", vp)])
+
 P = C.POINTER
 _SIGS = {
     "lav_last_error": (C.c_char_p, []),
@@ -192,6 +207,11 @@ _SIGS = {
     "lav_beam_step": (i32, [vp, i32, i32, i32, vp, i64, vp, i64, i32, f32, vp, vp, vp]),
     "lav_beam_select": (i32, [vp, P(BeamSelectDesc)]),
     "lav_beam_reparent": (i32, [vp, P(BeamReparentDesc)]),
+    # retrieval evaluation (csrc/retrieval.hip, csrc/stages.cpp)
+    "lav_attention_rows": (i32, [vp, i32, i32, i32, i32, vp, i64, vp, vp, f32, vp, i64]),
+    "lav_bert_layer_fwd_rows": (i32, [vp, P(BertLayerRowsDesc)]),
+    "lav_mlm_pair_readout": (i32, [vp, P(MlmPairReadoutDesc)]),
+    "lav_retrieval_rank": (i32, [vp, i32, i32, vp, i64, vp, vp]),
     # fp32-I/O validation mode (csrc/validate.hip)
     "lav_v_gemm_f32": (i32, [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i32, vp, i64]),
     "lav_v_attention_f32": (i32, [vp, P(AttnDesc), vp, vp, vp]),

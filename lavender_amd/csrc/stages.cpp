@@ -310,3 +310,50 @@ extern "C" int lav_bert_layer_decode_beam(void* stream, const lav_bert_layer_dec
                 beams, LAV_BEAM_MAX, d ? d->B : 0);
     return bert_layer_decode(stream, d, beams);
 }
+
+// One fusion layer of the retrieval pair scorer (eval_retrieval_mlm.py:185-206): the arithmetic of lav_bert_layer_fwd at eval with everything after
+// the QKV GEMM on the one [MASK] row per pair -- keys and values still come from every row.  M = n_seq rows takes the ordinary tile GEMM.
+extern "C" int lav_bert_layer_fwd_rows(void* stream, const lav_bert_layer_rows_desc* d) {
+    LAV_REQUIRE(d, "lav_bert_layer_fwd_rows: null descriptor");
+    LAV_REQUIRE(d->n_seq > 0 && d->L > 0 && d->hidden > 0 && d->heads > 0 && d->hidden == 64 * d->heads && d->ffn > 0,
+                "lav_bert_layer_fwd_rows: n_seq=%d L=%d hidden=%d heads=%d (hidden = 64 heads) ffn=%d", d->n_seq, d->L, d->hidden, d->heads, d->ffn);
+    LAV_REQUIRE(d->key_mask && d->q_row && d->x && d->res && d->res_rowmap && d->w_qkv && d->w_ao && d->w_ff1 && d->w_ff2 && d->qkv && d->cx &&
+                d->pre1 && d->mean1 && d->rstd1 && d->x1 && d->h && d->pre2 && d->y && d->y32, "lav_bert_layer_fwd_rows: null buffer");
+    LAV_REQUIRE(d->res_dtype >= 0 && d->res_dtype <= 2 && d->ldr >= d->hidden, "lav_bert_layer_fwd_rows: res_dtype=%d (0 bf16, 1 fp32, 2 fp16) ldr=%ld",
+                d->res_dtype, d->ldr);
+    const bool resln = d->res_mean != nullptr;
+    LAV_REQUIRE(!resln || (d->res_dtype != 0 && d->res_rstd && d->res_gamma && d->res_beta),
+                "lav_bert_layer_fwd_rows: res_mean needs fp32 / fp16 pre-LayerNorm rows and all of res_rstd / res_gamma / res_beta");
+    const int n = d->n_seq, R = d->n_seq * d->L, H = d->hidden, F = d->ffn;
+    {
+        lav_gemm_epilogue e = epi0();
+        e.bias = d->b_qkv; e.a_rowmap = d->x_rowmap;
+        LAV_TRY(lav_gemm_bf16(stream, 0, R, 3 * H, H, d->x, H, d->w_qkv, H, d->qkv, 3 * H, &e, 1));
+    }
+    LAV_TRY(lav_attention_rows(stream, n, d->L, d->heads, 64, d->qkv, 3 * H, d->key_mask, d->q_row, (float)pow(64.0, -0.5), d->cx, H));
+    {
+        lav_gemm_epilogue e = epi0();
+        e.bias = d->b_ao; e.out_mode = 1;
+        e.residual = d->res; e.ldr = d->ldr; e.residual_f32 = d->res_dtype; e.res_rowmap = d->res_rowmap;
+        if (resln) { e.res_ln_mean = d->res_mean; e.res_ln_rstd = d->res_rstd; e.res_ln_gamma = d->res_gamma; e.res_ln_beta = d->res_beta; }
+        LAV_TRY(lav_gemm_bf16(stream, 0, n, H, H, d->cx, H, d->w_ao, H, d->pre1, H, &e, 1));
+    }
+    lav_ln_f32 f32in; f32in.x_f32 = 1; f32in.y32 = nullptr; f32in.ldy32 = 0;
+    LAV_TRY(lav_layernorm_fwd(stream, n, H, d->pre1, H, nullptr, d->ln1_gamma, d->ln1_beta, d->ln_eps, d->x1, H, d->mean1, d->rstd1, &f32in));
+    {
+        lav_gemm_epilogue e = epi0();
+        e.bias = d->b_ff1; e.act = 1;
+        LAV_TRY(lav_gemm_bf16(stream, 0, n, F, H, d->x1, H, d->w_ff1, H, d->h, F, &e, 1));
+    }
+    {
+        lav_gemm_epilogue e = epi0();
+        e.bias = d->b_ff2; e.out_mode = 1;
+        e.residual = d->pre1; e.ldr = H; e.residual_f32 = 1;
+        e.res_ln_mean = d->mean1; e.res_ln_rstd = d->rstd1; e.res_ln_gamma = d->ln1_gamma; e.res_ln_beta = d->ln1_beta;
+        LAV_TRY(lav_gemm_bf16(stream, 0, n, H, F, d->h, F, d->w_ff2, F, d->pre2, H, &e, 1));
+    }
+    lav_ln_f32 f32o; f32o.x_f32 = 1; f32o.y32 = d->y32; f32o.ldy32 = H;
+    LAV_TRY(lav_layernorm_fwd(stream, n, H, d->pre2, H, nullptr, d->ln2_gamma, d->ln2_beta, d->ln2_eps > 0.f ? d->ln2_eps : d->ln_eps, d->y, H,
+                              d->mean2, d->rstd2, &f32o));
+    return LAV_OK;
+}

@@ -541,3 +541,84 @@ class PretrainLoader:
 
 def get_dl(ds, args, rank=0, world=1):
     return PretrainLoader(ds, args, rank=rank, world=world)
+
+
+# ---- text-to-video retrieval evaluation (eval_retrieval_mlm.py:50-73 on eval_retrieval_task_specific.py:7-58) ----------------------------------
+def clip_frame_indices(n_frames, size_frame, multi_clip, sampling):
+    """frame indices of each clip a test video yields (Dataset_RetrievalTsEval.get_clips_with_temporal_sampling): every frame when the row has
+    one frame or exactly size_frame; else size_frame positions over the whole row, or -- multi_clip_testing -- ceil(n / size_frame) clips,
+    clip k from frame k with that stride.  `sampling` is Dataset_Base.sampling."""
+    if n_frames == 1 or size_frame == n_frames:
+        return [list(range(n_frames))]
+    sf = min(size_frame, n_frames)
+    n_clips = int(math.ceil(n_frames / sf))
+    if multi_clip:
+        return [sampling(k, min(k + (sf - 1) * n_clips, n_frames - 1), sf) for k in range(n_clips)]
+    return [sampling(0, n_frames - 1, sf)]
+
+
+class Dataset_RetrievalMlmEval(Dataset_Base):
+    """eval_retrieval_mlm.py:50-73: the test split of a retrieval task -- img_{dataset}.tsv + img_{dataset}.id2lineidx.pkl + txt_{task}.json[split]
+    -- as (clips, txt + appended [MASK], mask, text id, video id) items; text id = position in the split (gt_txt2vid, :16-17).  The frames of a
+    clip are decoded by the GPU JPEG pipeline (FrameDecoder) in collate_batch; every frame is centre-cropped (or pad-resized) as in evaluation."""
+
+    def __init__(self, args, split="test", tokzr=None, data_dir=None):
+        import json
+        import pickle
+        super().__init__(args, split=split, size_frame=args.size_frame, tokzr=tokzr)
+        d = data_dir or args.data_dir
+        self.tsv = TsvFile(f"{d}/img_{args.dataset}.tsv")
+        self.id2lineidx = pickle.load(open(f"{d}/img_{args.dataset}.id2lineidx.pkl", "rb"))
+        self.txt = json.load(open(f"{d}/txt_{args.task}.json", "r"))[split]
+        self.gt_txt2vid = {idx: item["video"] for idx, item in enumerate(self.txt)}
+        self._decoder = None
+
+    @property
+    def prompt_text(self):
+        return "is the video-text paired, true or false?"
+
+    def __len__(self):
+        return len(self.txt)
+
+    def str2txt(self, s):
+        if isinstance(s, list):                            # several reference captions of one item are joined (Dataset_RetrievalTsEval)
+            s = " ".join(s)
+        txt, mask = super().str2txt(s)
+        return self.append_mask_tok2txt(txt, mask)
+
+    def _clip_plans(self, bufs):
+        """Dataset_RetrievalTsEval.get_img_or_video (eval_retrieval_task_specific.py:60-79): the given frames, no further sampling;
+        ["vid_rand_crop"] becomes one centre-crop window for the whole clip, ["pad_resize"] pads and resizes, anything else centre-crops"""
+        t = self.args.img_transform
+        if t == ["vid_rand_crop"]:
+            return self._plan_clip(bufs, False)
+        return [self._plan_one(b, "pad_resize" if t == ["pad_resize"] else "img_center_crop") for b in bufs]
+
+    def get_clips_with_temporal_sampling(self, list_of_b):
+        """[[FramePlan] per clip] of clip_frame_indices"""
+        return [self._clip_plans([list_of_b[i] for i in idx])
+                for idx in clip_frame_indices(len(list_of_b), self.size_frame, getattr(self.args, "multi_clip_testing", False), self.sampling)]
+
+    def __getitem__(self, idx):
+        item = self.txt[idx]
+        video_id = item["video"]
+        # id2lineidx holds the BYTE offset of the video's line (seek_img_tsv, dataset.py:44-46); field 0 is the id, field 1 is not a frame:
+        # the frames are the fields from 2 on (eval_retrieval_task_specific.py:86)
+        row = self.tsv.fields(self.id2lineidx[video_id])
+        clips = self.get_clips_with_temporal_sampling(row[2:])
+        txt, mask = self.str2txt(item["caption"])
+        return clips, txt, mask, idx, video_id
+
+    def collate_batch(self, inputs):
+        """{"img" (B, clips, T, 3, S, S) decoded on the GPU, "txt", "mask", "tid", "vid"} (eval_retrieval_mlm.py:65-73)"""
+        S = int(self.args.size_img)
+        clips = [c for c, _, _, _, _ in inputs]
+        nc, T = len(clips[0]), len(clips[0][0])
+        if any(len(c) != nc or any(len(p) != T for p in c) for c in clips):
+            raise ValueError("every item of a batch needs the same number of clips and frames (T.stack of the reference fails as well)")
+        if self._decoder is None:
+            self._decoder = FrameDecoder(4)
+        plans = [p for c in clips for clip in c for p in clip]
+        img = self._decoder.decode(plans, S).view(len(inputs), nc, T, 3, S, S)
+        return {"img": img, "txt": torch.stack([t for _, t, _, _, _ in inputs]), "mask": torch.stack([m for _, _, m, _, _ in inputs]),
+                "tid": [t for _, _, _, t, _ in inputs], "vid": [v for _, _, _, _, v in inputs]}

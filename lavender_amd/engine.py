@@ -1073,6 +1073,39 @@ def bert_layer_eval_c(x, resln_t, layer, c, key_mask, n, L):
     return y, (pre2, st2[0], st2[1], out.weight.data, out.bias.data), qkv
 
 
+
+def bert_layer_rows_eval(x, x32, layer, key_mask, n, L, q_row, res_rowmap, x_rowmap=None):
+    """The last fusion layer of the retrieval pair scorer (lav_bert_layer_fwd_rows): BertLayerFn's eval arithmetic with everything after the QKV
+    GEMM on row q_row[s] of every sequence s.  x / x32 are what model._encode hands the layer: x the bf16 input (n * L rows, or the un-expanded
+    pair source read through x_rowmap), x32 None (residual = x), an fp32 tensor, or RESLN's (pre, mean, rstd, gamma, beta).  res_rowmap (n,)
+    int32: the residual row of each selected row.  Returns (y bf16, y32 fp32), both (n, H)."""
+    Hd, dev, f32 = x.shape[1], x.device, torch.float32
+    arena = layer._arena()
+    att_m, ao, inter, outp = layer.attention.self, layer.attention.output, layer.intermediate, layer.output
+    wqkv16, _, _ = arena.fused_view(att_m.query.weight, 3 * Hd)
+    _, _, bqkv = arena.fused_view(att_m.query.bias, 3 * Hd)
+    F = inter.dense.weight.shape[0]
+    if isinstance(x32, tuple):
+        res, (rm, rr, rg, rb) = x32[0], x32[1:]
+    else:
+        res, rm, rr, rg, rb = (x32 if x32 is not None else x), None, None, None, None
+    res_dtype = {bf16: 0, f32: 1, torch.float16: 2}[res.dtype]
+    e = torch.empty
+    qkv = e((n * L, 3 * Hd), dtype=bf16, device=dev)
+    cx, x1, y = (e((n, Hd), dtype=bf16, device=dev) for _ in range(3))
+    pre1, pre2, y32 = (e((n, Hd), dtype=f32, device=dev) for _ in range(3))
+    st = e((4, n), dtype=f32, device=dev)
+    h = e((n, F), dtype=bf16, device=dev)
+    dp = K._dp
+    d = K.L.BertLayerRowsDesc(n, L, Hd, layer.num_heads, F, float(ao.LayerNorm.eps), float(outp.LayerNorm.eps), dp(key_mask), dp(q_row),
+                              dp(wqkv16), dp(bqkv), dp(W16(ao.dense.weight)), dp(ao.dense.bias.data), dp(ao.LayerNorm.weight.data),
+                              dp(ao.LayerNorm.bias.data), dp(W16(inter.dense.weight)), dp(inter.dense.bias.data), dp(W16(outp.dense.weight)),
+                              dp(outp.dense.bias.data), dp(outp.LayerNorm.weight.data), dp(outp.LayerNorm.bias.data), dp(x), dp(x_rowmap), dp(res),
+                              K._ld(res), res_dtype, dp(res_rowmap), dp(rm), dp(rr), dp(rg), dp(rb), dp(qkv), dp(cx), dp(pre1), dp(st[0]), dp(st[1]),
+                              dp(x1), dp(h), dp(pre2), dp(st[2]), dp(st[3]), dp(y), dp(y32))
+    K.bert_layer_fwd_rows(d)
+    return y, y32
+
 class MLMHeadFn(torch.autograd.Function):
     """BertOnlyMLMHead (main_pretrain_mlm.py:46-48,69,115): dense+GELU, LayerNorm, vocab projection."""
 

@@ -789,3 +789,32 @@ def beam_reparent_desc(src, dst, parent, max_len):
 def beam_reparent(desc, n_pos):
     desc.n_pos = n_pos
     L.check(L.lib.lav_beam_reparent(_s(), C.byref(desc)), "lav_beam_reparent")
+
+
+# ---- retrieval evaluation (csrc/retrieval.hip, csrc/stages.cpp) ----------------------------------------------------------------------
+def attention_rows(qkv, n, seq_len, heads, key_mask, q_row, out=None, scale=0.125):
+    """(n, heads * 64) bf16: attention of row q_row[s] of every sequence s over its L keys (qkv (n * L, 3 hidden) bf16, key_mask (n, L) int32,
+    q_row (n,) int32, both on the device): lav_attention_rows"""
+    H = heads * 64
+    if out is None:
+        out = torch.empty((n, H), dtype=bf16, device=qkv.device)
+    L.check(L.lib.lav_attention_rows(_s(), n, seq_len, heads, 64, _p(qkv), _ld(qkv), _p(key_mask), _p(q_row), float(scale), _p(out), _ld(out)),
+            "lav_attention_rows")
+    return out
+
+
+def bert_layer_fwd_rows(desc):
+    L.check(L.lib.lav_bert_layer_fwd_rows(_s(), C.byref(desc)), "lav_bert_layer_fwd_rows")
+
+
+def mlm_pair_readout(desc):
+    L.check(L.lib.lav_mlm_pair_readout(_s(), C.byref(desc)), "lav_mlm_pair_readout")
+
+
+def retrieval_rank(S, gt, out=None):
+    """(n_text,) int32 1-based rank of column gt[t] in row t of the fp32 score matrix S (stable, NaN last): lav_retrieval_rank"""
+    nt, nv = S.shape
+    if out is None:
+        out = torch.empty(nt, dtype=torch.int32, device=S.device)
+    L.check(L.lib.lav_retrieval_rank(_s(), nt, nv, _p(S), _ld(S), _p(gt), _p(out)), "lav_retrieval_rank")
+    return out

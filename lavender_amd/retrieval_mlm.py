@@ -2,6 +2,9 @@
 
 Text-to-video retrieval posed as masked-LM: every one of the B x B (video i, text j) pairs is run through the
 fusion encoder and the MLM head; the appended [MASK] position is trained to say "true" when vid[i] == vid[j]."""
+import os
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -89,6 +92,26 @@ class Agent_Retrieval_MLM(Agent_Base):
         return self.reduce_mean(float(np.average(ret)))
 
 
+# Pair scorer of the retrieval evaluation: the last fusion layer and the MLM head run on the [MASK] row of each pair only (lav_bert_layer_fwd_rows,
+# lav_mlm_pair_readout).  LAV_RET_ROWS=0 runs the full last layer and the full-vocabulary head and slices the two columns instead: the
+# reference's formulation on this engine, for A/B.
+RET_ROWS = os.environ.get("LAV_RET_ROWS", "1") != "0"
+
+
+@dataclass
+class PairSource:
+    """What LAVENDER_RetrievalMlmEval.pair_source builds once for a whole evaluation: the un-expanded (U, H) rows [every video's Lv rows ;
+    every text's X rows] that the first fusion layer reads through the pair map, the int64 key masks, and each text's [MASK] row."""
+    src: torch.Tensor
+    mask_img: torch.Tensor
+    mask_txt: torch.Tensor
+    n_video: int
+    Lv: int
+    n_text: int
+    X: int
+    q_row: np.ndarray                                  # (n_text,) int64: position of the [MASK] token within the text rows
+
+
 class LAVENDER_RetrievalMlmEval(LAVENDER_Retrieval_MLM):
     """Two-phase retrieval inference of the reference (eval_retrieval_mlm.py:10-47): 'feat' encodes every video once
     (mean over its clips) and every caption once; 'cross' runs the fusion encoder + MLM head on (video, text) pairs
@@ -125,3 +148,110 @@ class LAVENDER_RetrievalMlmEval(LAVENDER_Retrieval_MLM):
             out, _ = self.go_cross(feat_img, mask_img, feat_txt, mask_txt)
             return self.fc_mtm(out[:, feat_img.shape[1]:]), batch.get("txt")
         raise ValueError(f"typ must be 'feat' or 'cross', got {typ!r}")
+
+    # ---- pair scorer (eval_retrieval_mlm.py:185-206 without the (pairs, X, vocab) logits) ---------------------------------------------------
+    def pair_source(self, feat_img, mask_img, feat_txt, mask_txt, txt):
+        """PairSource of 'feat' outputs: feat_img (M_v, Lv, H), mask_img (M_v, Lv), feat_txt (N_t, X, H), mask_txt / txt (N_t, X).  Each text
+        must hold exactly one [MASK] token (the reference asserts one score per pair, eval_retrieval_mlm.py:207-208): ValueError otherwise.
+        Features in go_feat's single buffer are used in place; separate tensors are joined by ONE copy here, never per chunk."""
+        from . import engine as E
+        Mv, Lv, Hd = feat_img.shape
+        Nt, X = txt.shape
+        if feat_txt.shape[:2] != (Nt, X) or mask_txt.shape != (Nt, X) or mask_img.shape != (Mv, Lv):
+            raise ValueError(f"pair_source: feat_img {tuple(feat_img.shape)} / mask_img {tuple(mask_img.shape)} / feat_txt {tuple(feat_txt.shape)} / "
+                             f"mask_txt {tuple(mask_txt.shape)} / txt {tuple(txt.shape)} do not agree")
+        mask_id = getattr(self, "mask_token_id", None)
+        if mask_id is None:
+            raise ValueError("pair_source: the model has no [MASK] id (build it with a tokenizer)")
+        hit = (txt.detach().to("cpu") == int(mask_id))
+        cnt = hit.sum(1)
+        bad = torch.nonzero(cnt != 1).flatten()
+        if bad.numel():
+            t = int(bad[0])
+            raise ValueError(f"pair_source: text {t} holds {int(cnt[t])} [MASK] tokens; every text needs exactly one (Dataset_RetrievalMlmEval "
+                             f"appends it)")
+        q_row = hit.to(torch.int64).argmax(1).numpy()
+        if E.rows_adjacent(feat_img, feat_txt):
+            src = E.JoinRowsFn.apply(feat_img, feat_txt)
+        else:
+            src = torch.cat([feat_img.reshape(Mv * Lv, Hd), feat_txt.reshape(Nt * X, Hd).to(feat_img.dtype)], 0)
+        return PairSource(src, mask_img.to(torch.int64).contiguous(), mask_txt.to(torch.int64).contiguous(), Mv, Lv, Nt, X, q_row)
+
+    def score_pairs(self, src, vi, ti, out=None, logits=None, out_rows=None):
+        """Scores p_true / (p_true + p_false) of the pairs (video vi[k], text ti[k]) of a PairSource (eval_retrieval_mlm.py:185-206), fp32 on
+        the device.  out=None: returns the (n,) scores; else they are written to out[out_rows[k], vi[k]] (out_rows defaults to ti) and out is
+        returned.  logits: an (n, 2) fp32 buffer for (p_true, p_false).  Nothing here waits for the device."""
+        from . import engine as E
+        from . import hip as K
+        if torch.is_grad_enabled() or self.training:
+            raise RuntimeError("score_pairs is evaluation only: call model.eval() and run it under torch.no_grad()")
+        vi = np.ascontiguousarray(vi, dtype=np.int64).reshape(-1)
+        ti = np.ascontiguousarray(ti, dtype=np.int64).reshape(-1)
+        n = len(vi)
+        if n == 0 or len(ti) != n:
+            raise ValueError(f"score_pairs: {n} video and {len(ti)} text indices")
+        if vi.min() < 0 or vi.max() >= src.n_video or ti.min() < 0 or ti.max() >= src.n_text:
+            raise ValueError(f"score_pairs: index outside the {src.n_video} videos / {src.n_text} texts of the pair source")
+        dev, Hd = src.src.device, src.src.shape[1]
+        Lv, X = src.Lv, src.X
+        L = Lv + X
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev, non_blocking=True)
+        if out is None:
+            S = torch.empty((1, n), dtype=torch.float32, device=dev)
+            rows, cols = np.zeros(n, dtype=np.int64), np.arange(n)
+        else:
+            S = out
+            assert S.dtype == torch.float32 and S.dim() == 2 and S.stride(1) == 1
+            rows, cols = (ti if out_rows is None else np.asarray(out_rows, dtype=np.int64).reshape(-1)), vi
+            if rows.min() < 0 or rows.max() >= S.shape[0] or cols.max() >= S.shape[1]:
+                raise ValueError(f"score_pairs: output index outside the {tuple(S.shape)} score matrix")
+        if logits is not None:
+            assert logits.dtype == torch.float32 and logits.shape == (n, 2) and logits.is_contiguous()
+        arena = self.arena()
+        arena.sync_half_if_stale()
+        flat = E.pair_index(src.n_video, Lv, src.n_text, X, vi, ti).reshape(-1)
+        km = K.pair_key_mask(src.mask_img, src.mask_txt, vi, ti)
+        if E.pair_fused_ok(Hd):
+            x, pair = src.src, (up(flat), None, None)
+        else:                                               # the map-reading GEMM tiles do not apply: this chunk's pairs gathered once
+            x, pair = K.gather_rows(src.src, up(flat), n * L, Hd), None
+        layers = self.trsfr.layer
+        last = len(layers) - 1
+        x32 = None
+        for i, lyr in enumerate(layers[:last]):            # model._encode's layer loop (eval: no dropout)
+            o = E.BertLayerFn.apply(arena.anchor, x, x32, lyr, km, n, L, 0.0, 0.0, True, 0, pair if i == 0 else None)
+            if len(o) == 4:
+                ln = lyr.output.LayerNorm
+                x, x32 = o[0], (o[1], o[2], o[3], ln.weight.data, ln.bias.data)
+            else:
+                x, x32 = o
+        first = pair if last == 0 else None
+        q = Lv + src.q_row[ti]                              # the [MASK] row of every pair within its sequence
+        tid_true, tid_false = int(self.true_token_id), int(self.false_token_id)
+        if not RET_ROWS:
+            o = E.BertLayerFn.apply(arena.anchor, x, x32, layers[last], km, n, L, 0.0, 0.0, False, 0, first)
+            out_l = self.fc_mtm(o[0].view(n, L, Hd)[:, Lv:])       # (n, X, vocab): the reference's logit block
+            kk = torch.arange(n, device=dev)
+            qq = torch.from_numpy(q - Lv).to(dev)
+            pt = out_l[kk, qq, tid_true].float()
+            pf = out_l[kk, qq, tid_false].float()
+            S[torch.from_numpy(rows).to(dev), torch.from_numpy(cols).to(dev)] = pt / (pt + pf)
+            if logits is not None:
+                logits[:, 0] = pt
+                logits[:, 1] = pf
+            return S[0] if out is None else S
+        sel = np.arange(n, dtype=np.int64) * L + q
+        res_map = flat[sel] if first is not None else sel
+        y, _ = E.bert_layer_rows_eval(x, x32, layers[last], km, n, L, up(q), up(res_map), x_rowmap=first[0] if first is not None else None)
+        pred = self.fc_mtm.predictions
+        tr, dec = pred.transform, pred.decoder
+        t = torch.empty((n, Hd), dtype=torch.float32, device=dev)
+        w_dec = E.W16(dec.weight)
+        rows_d, cols_d = up(rows), up(cols)
+        d = K.L.MlmPairReadoutDesc(n, Hd, dec.weight.shape[0], tid_true, tid_false, float(tr.LayerNorm.eps), y.data_ptr(), K._ld(y),
+                                   E.W16(tr.dense.weight).data_ptr(), tr.dense.bias.data.data_ptr(), tr.LayerNorm.weight.data.data_ptr(),
+                                   tr.LayerNorm.bias.data.data_ptr(), w_dec.data_ptr(), K._ld(w_dec), dec.bias.data.data_ptr(), t.data_ptr(),
+                                   rows_d.data_ptr(), cols_d.data_ptr(), S.data_ptr(), K._ld(S), S.shape[0], S.shape[1],
+                                   K._dp(logits))
+        K.mlm_pair_readout(d)
+        return S[0] if out is None else S
