@@ -145,8 +145,21 @@ int lav_gemm_tn_grouped(void* stream, int n_jobs, const lav_gemm_tn_job* jobs, i
 /* Tuning / probe hook: selects between kernel variants at run time (within-process A/B measurements in tools/): which 2 = ping-pong
  * weight-gradient kernel on/off, 5 = probe bits of the 256x256 kernel (timing only, wrong results), 6 = column-group width of the tile
  * walk, 7 / 9 = 192-row tiles / their loader-wave form on/off, 11 = phase-shifted two-group tile (bit 0: 256-row, bit 1: 192-row;
- * results bit-identical to the tiles it replaces).  Returns the previous value, -1 for an unknown selector.  Results are identical up to fp32 summation order (except selector 5). */
+ * results bit-identical to the tiles it replaces), 12 = fewest output rows for the 256-row weight-gradient tiles (LAV_GEMM_TN_MINM).  Returns the
+ * previous value, -1 for an unknown selector.  Results are identical up to fp32 summation order (except selector 5). */
 int lav_gemm_select(int which, int value);
+/* Probe hooks, not part of the contract: the launches lav_gemm_bf16 / lav_gemm_tn_grouped would make for a call, in order, without making them (no
+ * device is needed; tests/ compare the route with their host copy of it).  Arguments as for those entries minus the stream and the operand
+ * pointers (lav_gemm_tn_job.A / B / C may be NULL); pointers of the epilogue are only tested for presence.  Writes at most max_out entries and
+ * returns the number of launches (1 ... 4, grouped fallback: up to 16), or the error code the entry itself would return for the call. */
+typedef struct lav_gemm_launch_info {
+    const char* kernel;           /* the kernel's name without template arguments, e.g. "gemm_ps_kernel" */
+    int tile_rows, tile_cols;     /* output tile of the launch (a reduction: the tile of the partial sums it reads) */
+    unsigned grid, block;         /* workgroups, threads per workgroup */
+} lav_gemm_launch_info;
+int lav_gemm_plan(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits,
+                  lav_gemm_launch_info* out, int max_out);
+int lav_gemm_tn_grouped_plan(int n_jobs, const lav_gemm_tn_job* jobs, int splits, lav_gemm_launch_info* out, int max_out);
 /* Same kind of hook for the large-window attention kernels (windows of 257 ... 768 tokens, attention_winl.hip): parts = 0 lets the library split
  * a problem into query parts by its own rule (the default), 1 / 3 force that many, -1 routes large windows to the generic kernels (tests compare
  * the two).  Process-wide; returns the previous value. */
@@ -740,12 +753,15 @@ int lav_retrieval_rank(void* stream, int n_text, int n_video, const float* S, lo
  *   weight-gradient kernel), LAV_GEMM_TN_MINM (fewest output rows for the 256-row weight-gradient tiles, default 160),
  *   LAV_GEMM_TN_GROUP (0: grouped weight-gradient launches run job by job), LAV_GEMM_GROUP_N (column-group width of the 256x256 tile
  *   walk), LAV_GEMM_H192 / LAV_GEMM_H192L (0: no 192-row tiles / no loader waves), LAV_GEMM_PS (bit 0 / bit 1: phase-shifted two-group form of
- *   the 256-row / 192-row tile, default 3), LAV_NT_STORES (bit 0: GELU' stored non-temporally,
- *   bit 2: loaded non-temporally; cross-entropy gradient stores), LAV_GEMM_DBG (timing ablations of the 256x256 kernel: WRONG results),
+ *   the 256-row / 192-row tile, default 3), LAV_NT_STORES (read twice, with different defaults: by the GEMM epilogue, default 5 -- bit 0: GELU'
+ *   stored non-temporally, bit 2: loaded non-temporally; by lav_adamw_step, default 1 -- bit 1: non-temporal parameter / moment
+ *   stores), LAV_GEMM_DBG (timing ablations of the 256x256 kernel: WRONG results),
  *   LAV_LN_ATOMIC_FLUSH (LayerNorm backward column sums by per-block atomics), LAV_LN_G32 (bit 0 / bit 1: 32-lane x 3-chunk rows for C = 768 in the
  *   forward / backward, default 1), LAV_WIN_BWD1 (0: window attention backward as the two
  *   round-3 passes instead of the one-pass kernel), LAV_WINL / LAV_SEQL (0: large windows / long sequences on the generic kernels).
- * lav_gemm_select(which, value) changes the GEMM ones of these at run time (same caveat: process-wide, for probes).
+ * lav_gemm_select(which, value) changes these GEMM ones at run time (same caveat: process-wide, for probes): 2 = LAV_GEMM_PP_TN, 5 = LAV_GEMM_DBG,
+ * 6 = LAV_GEMM_GROUP_N, 7 = LAV_GEMM_H192, 9 = LAV_GEMM_H192L, 11 = LAV_GEMM_PS, 12 = LAV_GEMM_TN_MINM; the others (LAV_GEMM_TN_KIND,
+ * LAV_GEMM_TN_GROUP, LAV_NT_STORES) are fixed when the library is loaded.
  * lav_probe_win_prof(buf): NULL = off; else the next stage-2-sized window backward runs the s_memtime-stamped build of win_bwd1 and
  * writes 160 uint64 stamps to the device buffer `buf` (tools/win_prof.py; profiles/r05_win_bwd1.md).
  * --------------------------------------------------------------------------------------------- */

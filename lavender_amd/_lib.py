@@ -42,6 +42,10 @@ class GemmTnJob(C.Structure):             # struct lav_gemm_tn_job
                 ("rowsum_a", vp), ("k_keep", vp), ("k_rows_per_group", i32), ("alpha", f32), ("fallback_splits", i32), ("assign", i32)]
 
 
+class GemmLaunchInfo(C.Structure):        # struct lav_gemm_launch_info (lav_gemm_plan / lav_gemm_tn_grouped_plan)
+    _fields_ = [("kernel", C.c_char_p), ("tile_rows", i32), ("tile_cols", i32), ("grid", u32), ("block", u32)]
+
+
 class LnGather(C.Structure):
     _fields_ = [("mode", i32), ("H", i32), ("W", i32), ("C0", i32)]
 
@@ -150,6 +154,8 @@ _SIGS = {
     "lav_winl_select": (i32, [i32]),
     "lav_probe_win_prof": (None, [vp]),
     "lav_gemm_tn_grouped": (i32, [vp, i32, P(GemmTnJob), i32]),
+    "lav_gemm_plan": (i32, [i32, i32, i32, i32, i64, i64, i64, P(GemmEpilogue), i32, P(GemmLaunchInfo), i32]),
+    "lav_gemm_tn_grouped_plan": (i32, [i32, P(GemmTnJob), i32, P(GemmLaunchInfo), i32]),
     "lav_bert_layer_fwd": (i32, [vp, P(BertLayerDesc)]),
     "lav_bert_layer_bwd": (i32, [vp, vp, P(BertLayerBwdDesc)]),
     "lav_swin_block_fwd": (i32, [vp, P(SwinBlockDesc)]),

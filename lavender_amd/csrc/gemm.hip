@@ -1647,129 +1647,164 @@ __global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(const float* __
     *(uint4*)(C + (long)row * ldc + col) = pack8(v);
 }
 
+// =================================================================================================================================
+// Host side: the process-wide switches, the route plan (pure: the CPU tests call it through lav_gemm_plan), the kernel table and the entries.
+// =================================================================================================================================
+
 // split-K partial tiles live in the stream's LAV_WS_SPLITK workspace (runtime.cpp: registered by the caller with lav_set_workspace, or one internal
 // allocation per stream).  Calls on the SAME stream are ordered, so they share it.
 static float* splitk_workspace(void* stream, size_t bytes) { return (float*)lav_ws_get(stream, LAV_WS_SPLITK, bytes, nullptr); }
 
-static const int lav_gemm_tn_kind = getenv("LAV_GEMM_TN_KIND") ? atoi(getenv("LAV_GEMM_TN_KIND")) : -1;   // probe hook: 0 = 128x128 only, 1 = at most 256x128, default = largest tile that fits
-static bool lav_gemm_pp_tn = getenv("LAV_GEMM_PP_TN") ? atoi(getenv("LAV_GEMM_PP_TN")) != 0 : true;   // ping-pong kernel for the 256x256 weight-gradient tiles
-// tile walk of the 256x256 K-contiguous kernel: column groups of 4 tiles when the output is >= 8 tiles wide (an XCD's 32 resident
-// tiles then form an 8 x 4 block: 12 operand panels in its L2 instead of 15 for 2.7 rows x 12 columns; measured +8-12 % on the
-// 45120 x 3072 x 768 GEMMs and on 8192^3, nothing on narrower outputs).  LAV_GEMM_GROUP_N=0 restores n-fastest, other values force G.
-static int lav_gemm_group_n = getenv("LAV_GEMM_GROUP_N") ? atoi(getenv("LAV_GEMM_GROUP_N")) : -1;
-static int lav_gemm_h192 = getenv("LAV_GEMM_H192") ? atoi(getenv("LAV_GEMM_H192")) : 1;          // 192-row tiles for outputs that under-fill the last round of 256-row tiles
-static int lav_gemm_h192l = getenv("LAV_GEMM_H192L") ? atoi(getenv("LAV_GEMM_H192L")) : 1;                         // 192-row tiles: two loader waves issue the operand DMA (0 = off)
-static int lav_gemm_ps = getenv("LAV_GEMM_PS") ? atoi(getenv("LAV_GEMM_PS")) : 3;                                 // phase-shifted 256 x 256 kernel instead of gemm_huge for the specialised layout-0 epilogues (round 6: -2.0 ms per cfg2 step; 0 = gemm_huge)
-static int lav_gemm_dbg = getenv("LAV_GEMM_DBG") ? atoi(getenv("LAV_GEMM_DBG")) : 0;                               // probe hook: GemmArgs.dbg of the 256x256 kernel
-extern "C" int lav_gemm_select(int which, int value) {    // probe hook (within-process A/B): which 0 = ping-pong kernel on/off; returns the old value
-    int old = -1;
-    if (which == 2) { old = lav_gemm_pp_tn; lav_gemm_pp_tn = value != 0; }
-    if (which == 5) { old = lav_gemm_dbg; lav_gemm_dbg = value; }
-    if (which == 6) { old = lav_gemm_group_n; lav_gemm_group_n = value; }
-    if (which == 7) { old = lav_gemm_h192; lav_gemm_h192 = value; }
-    if (which == 9) { old = lav_gemm_h192l; lav_gemm_h192l = value; }
-    if (which == 11) { old = lav_gemm_ps; lav_gemm_ps = value; }
+// ---- switches: read from the environment once, when the library is loaded; lav_gemm_select changes the numbered ones at run time ------------
+struct GemmSwitches {
+    int tn_kind;     // LAV_GEMM_TN_KIND: 0 = 128x128 weight-gradient tiles only, 1 = at most 256x128, default = largest tile that fits
+    int pp_tn;       // LAV_GEMM_PP_TN (select 2): ping-pong kernel for the 256x256 weight-gradient tiles
+    int dbg;         // LAV_GEMM_DBG (select 5): GemmArgs.dbg of the 256x256 kernel (timing only, wrong results)
+    // tile walk of the 256x256 K-contiguous kernel: column groups of 4 tiles when the output is >= 8 tiles wide (an XCD's 32 resident
+    // tiles then form an 8 x 4 block: 12 operand panels in its L2 instead of 15 for 2.7 rows x 12 columns; measured +8-12 % on the
+    // 45120 x 3072 x 768 GEMMs and on 8192^3, nothing on narrower outputs).  0 restores n-fastest, other values force G, < 0 = that rule.
+    int group_n;     // LAV_GEMM_GROUP_N (select 6)
+    int h192;        // LAV_GEMM_H192 (select 7): 192-row tiles for outputs that under-fill the last round of 256-row tiles
+    int h192l;       // LAV_GEMM_H192L (select 9): 192-row tiles: two loader waves issue the operand DMA (0 = off)
+    int ps;          // LAV_GEMM_PS (select 11): phase-shifted kernel instead of gemm_huge (bit 0) / gemm_h192l (bit 1) for the specialised layout-0 epilogues (round 6: -2.0 ms per cfg2 step)
+    int tn_min_m;    // LAV_GEMM_TN_MINM (select 12): fewest output rows that take the 256-row weight-gradient tiles (outputs with 160 ... 255 rows, Swin-L stage 0: C = 192,
+                     // leave a quarter of the tile idle and are still well ahead of the 128 x 128 kernel; 256 restores the old threshold)
+    int tn_group;    // LAV_GEMM_TN_GROUP: 0 = lav_gemm_tn_grouped runs its jobs one by one
+    int nt_stores;   // LAV_NT_STORES: 1: GELU' stored non-temporally, 4: and loaded non-temporally by the gradient epilogue (73.30 -> 73.12 ms per step, two interleaved pairs)
+};
+static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+static GemmSwitches gemm_sw = {env_int("LAV_GEMM_TN_KIND", -1), env_int("LAV_GEMM_PP_TN", 1) != 0, env_int("LAV_GEMM_DBG", 0), env_int("LAV_GEMM_GROUP_N", -1),
+                               env_int("LAV_GEMM_H192", 1), env_int("LAV_GEMM_H192L", 1), env_int("LAV_GEMM_PS", 3), env_int("LAV_GEMM_TN_MINM", 160),
+                               env_int("LAV_GEMM_TN_GROUP", 1) != 0, env_int("LAV_NT_STORES", 5)};
+// probe hook (within-process A/B): which = 2 pp_tn, 5 dbg, 6 group_n, 7 h192, 9 h192l, 11 ps, 12 tn_min_m; returns the old value, -1 for an unknown id
+extern "C" int lav_gemm_select(int which, int value) {
+    int* const p = which == 2 ? &gemm_sw.pp_tn : which == 5 ? &gemm_sw.dbg : which == 6 ? &gemm_sw.group_n : which == 7 ? &gemm_sw.h192 :
+                   which == 9 ? &gemm_sw.h192l : which == 11 ? &gemm_sw.ps : which == 12 ? &gemm_sw.tn_min_m : nullptr;
+    if (!p) return -1;
+    const int old = *p;
+    *p = which == 2 ? value != 0 : value;
     return old;
 }
 
-extern "C" int lav_gemm_bf16(void* stream, int layout, int M, int N, int K, const void* A, long lda, const void* B,
-                             long ldb, void* C, long ldc, const lav_gemm_epilogue* epi, int splits) {
-    LAV_REQUIRE(M > 0 && N > 0 && K > 0, "lav_gemm_bf16: empty problem M=%d N=%d K=%d", M, N, K);
-    LAV_REQUIRE(layout >= 0 && layout <= 2, "lav_gemm_bf16: bad layout %d", layout);
-    LAV_REQUIRE(A && B && C, "lav_gemm_bf16: null operand");
-    LAV_REQUIRE((lda % 8) == 0 && (ldb % 8) == 0, "lav_gemm_bf16: lda/ldb must be multiples of 8 (16-byte rows)");
-    LAV_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)C % 16) == 0,
-                "lav_gemm_bf16: operands must be 16-byte aligned");
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = C;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    if (epi) g.e = *epi; else { g.e.alpha = 1.f; }
-    g.assign = g.e.assign != 0;
-    LAV_REQUIRE(!g.assign || (layout == 2 && g.e.out_mode == 2), "lav_gemm_bf16: assign is defined for weight gradients only (layout 2, out_mode 2)");
-    static const int nt_stores = getenv("LAV_NT_STORES") ? atoi(getenv("LAV_NT_STORES")) : 5;   // 1: GELU' stored non-temporally, 4: and loaded non-temporally by the gradient epilogue (73.30 -> 73.12 ms per step, two interleaved pairs)
-    g.nt_preact = (nt_stores & 1) | ((nt_stores & 4) ? 2 : 0);
-    if (g.e.alpha == 0.f) g.e.alpha = 1.f;
-    if (splits < 1) splits = 1;
-    LAV_REQUIRE(!g.e.rowsum_a || layout == 2, "lav_gemm_bf16: rowsum_a is only defined for layout 2 (TN)");
-    const bool no_epilogue = !g.e.bias && !g.e.act && !g.e.preact && !g.e.gelu_in && g.e.dropout_p <= 0.f && !g.e.row_scale &&
-                             !g.e.residual && !g.e.colsum && !g.e.rowsum_a && g.e.alpha == 1.f;
-    LAV_REQUIRE(splits == 1 || g.e.out_mode == 2 || (g.e.out_mode == 0 && layout != 2 && no_epilogue && (N % 8) == 0),
-                "lav_gemm_bf16: split-K needs out_mode=2 (fp32 accumulate), or a bf16 output without epilogue and N %% 8 == 0");
-    LAV_REQUIRE(g.e.out_mode != 0 || (ldc % 8) == 0, "lav_gemm_bf16: bf16 output needs ldc %% 8 == 0");
-    LAV_REQUIRE(g.e.hm_heads <= 0 || (g.e.out_mode == 0 && layout != 2 && splits == 1 && g.e.hm_head_dim > 0 && (g.e.hm_head_dim % 8) == 0 &&
-                                      (N % (g.e.hm_heads * g.e.hm_head_dim)) == 0 && g.e.hm_rows >= M),
-                "lav_gemm_bf16: head-major store needs a bf16 output, layout 0 / 1, no split-K, hm_head_dim %% 8 == 0, N %% (hm_heads * hm_head_dim) == 0 and hm_rows >= M");
-    LAV_REQUIRE(g.e.out_mode == 0 || g.e.out_mode == 3 || (ldc % 4) == 0, "lav_gemm_bf16: fp32 output needs ldc %% 4 == 0");
-    LAV_REQUIRE(g.e.out_mode != 3 || ((ldc % 8) == 0 && layout != 2 && splits == 1), "lav_gemm_bf16: fp16 output needs ldc %% 8 == 0, layout 0 / 1, no split-K");
-    int kps = ((K + splits - 1) / splits + BKT - 1) / BKT * BKT;
-    g.k_per_split = kps;
-    splits = (K + kps - 1) / kps;
-    g.drop_thresh = lav_drop_thresh(g.e.dropout_p);
-    int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    g.splits = splits;
-    dim3 grid(tiles * splits), block(NT_);
-    hipStream_t s = (hipStream_t)stream;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)gemm_kernel<true, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-        hipFuncSetAttribute((const void*)gemm_kernel<true, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-        hipFuncSetAttribute((const void*)gemm_kernel<false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+// ---- kernel table: every instantiation the plan can name, its launch constants, and whether its dynamic-LDS limit has been raised yet -------
+constexpr unsigned S_B = EF_BIAS, S_BG = EF_BIAS | EF_ACT, S_GC = EF_GIN | EF_RSCALE | EF_COLSUM, S_BDR = EF_BIAS | EF_DROP | EF_RSCALE | EF_RES,
+                   S_BDRO = S_BDR | EF_O32;
+constexpr int FI_ALL = 5;                                    // feature-set index: S_B, S_BG, S_GC, S_BDR, S_BDRO, EF_ALL (the generic code)
+enum GemmKernelId : int {
+    GK_SMALL = 0,                                            // gemm_kernel: + layout (0 NT, 1 NN, 2 TN with the generic epilogue)
+    GK_PS256 = GK_SMALL + 3,                                 // + feature index (specialised sets only)
+    GK_HUGE = GK_PS256 + 5,                                  // + 2 * feature index + layout
+    GK_PS192 = GK_HUGE + 12,                                 // + feature index (specialised sets only)
+    GK_H192 = GK_PS192 + 5,                                  // + 3 * feature index (specialised sets only) + {0: loader-wave form (NT), 1: NT, 2: NN}
+    GK_BIG = GK_H192 + 15,                                   // + 2 * feature index + layout
+    GK_PP_TN = GK_BIG + 12, GK_HUGE_TN, GK_BIG_TN, GK_SMALL_TN,          // weight gradients with the flush epilogue
+    GK_PP_GROUP, GK_TN_REDUCE, GK_TN_REDUCE_GROUP, GK_SPLITK_REDUCE, GK_COUNT
+};
+struct GemmKernel { const void* fn; const char* name; int threads, lds; bool attr_done; };
+template <bool AKC, bool BKC, int KG, unsigned F = EF_ALL> static GemmKernel k_small() { return {(const void*)gemm_kernel<AKC, BKC, KG, F>, "gemm_kernel", NT_ * KG, KG == 1 ? GEMM_LDS_BYTES : 131072}; }
+template <bool AKC, bool BKC, unsigned F> static GemmKernel k_big() { return {(const void*)gemm_big_kernel<AKC, BKC, F>, "gemm_big_kernel", 512, BIG_LDS}; }
+template <bool AKC, bool BKC, unsigned F> static GemmKernel k_huge() { return {(const void*)gemm_huge_kernel<AKC, BKC, F>, "gemm_huge_kernel", 512, HUGE_LDS}; }
+template <bool BKC, unsigned F> static GemmKernel k_h192() { return {(const void*)gemm_h192_kernel<true, BKC, F>, "gemm_h192_kernel", 512, HUGE_LDS}; }
+template <unsigned F> static GemmKernel k_h192l() { return {(const void*)gemm_h192l_kernel<true, true, F>, "gemm_h192l_kernel", 640, HUGE_LDS}; }
+template <unsigned F, int RF> static GemmKernel k_ps() { return {(const void*)gemm_ps_kernel<F, RF>, "gemm_ps_kernel", 512, HUGE_LDS}; }
+static GemmKernel gemm_kernels[] = {
+    k_small<true, true, 1>(), k_small<true, false, 1>(), k_small<false, false, 2>(),
+    k_ps<S_B, 8>(), k_ps<S_BG, 8>(), k_ps<S_GC, 8>(), k_ps<S_BDR, 8>(), k_ps<S_BDRO, 8>(),
+    k_huge<true, true, S_B>(), k_huge<true, false, S_B>(), k_huge<true, true, S_BG>(), k_huge<true, false, S_BG>(),
+    k_huge<true, true, S_GC>(), k_huge<true, false, S_GC>(), k_huge<true, true, S_BDR>(), k_huge<true, false, S_BDR>(),
+    k_huge<true, true, S_BDRO>(), k_huge<true, false, S_BDRO>(), k_huge<true, true, EF_ALL>(), k_huge<true, false, EF_ALL>(),
+    k_ps<S_B, 6>(), k_ps<S_BG, 6>(), k_ps<S_GC, 6>(), k_ps<S_BDR, 6>(), k_ps<S_BDRO, 6>(),
+    k_h192l<S_B>(), k_h192<true, S_B>(), k_h192<false, S_B>(), k_h192l<S_BG>(), k_h192<true, S_BG>(), k_h192<false, S_BG>(),
+    k_h192l<S_GC>(), k_h192<true, S_GC>(), k_h192<false, S_GC>(), k_h192l<S_BDR>(), k_h192<true, S_BDR>(), k_h192<false, S_BDR>(),
+    k_h192l<S_BDRO>(), k_h192<true, S_BDRO>(), k_h192<false, S_BDRO>(),
+    k_big<true, true, S_B>(), k_big<true, false, S_B>(), k_big<true, true, S_BG>(), k_big<true, false, S_BG>(),
+    k_big<true, true, S_GC>(), k_big<true, false, S_GC>(), k_big<true, true, S_BDR>(), k_big<true, false, S_BDR>(),
+    k_big<true, true, S_BDRO>(), k_big<true, false, S_BDRO>(), k_big<true, true, EF_ALL>(), k_big<true, false, EF_ALL>(),
+    {(const void*)gemm_pp_kernel<true, EF_TNFLUSH>, "gemm_pp_kernel", 512, PP_LDS},
+    k_huge<false, false, EF_TNFLUSH>(), k_big<false, false, EF_TNFLUSH>(), k_small<false, false, 2, EF_TNFLUSH>(),
+    {(const void*)gemm_pp_group_kernel<true, EF_TNFLUSH>, "gemm_pp_group_kernel", 512, PP_LDS},
+    {(const void*)tn_reduce_kernel, "tn_reduce_kernel", 256, 0},
+    {(const void*)tn_reduce_group_kernel, "tn_reduce_group_kernel", 256, 0},
+    {(const void*)splitk_reduce_bf16_kernel, "splitk_reduce_bf16_kernel", 256, 0},
+};
+static_assert(sizeof(gemm_kernels) / sizeof(gemm_kernels[0]) == GK_COUNT, "gemm_kernels must hold one row per GemmKernelId");
+
+// one launch: which kernel, how many blocks, and the output tile it works in (what lav_gemm_plan reports); kern < 0 = no launch
+struct GemmLaunch { int kern; unsigned grid; int tile_m, tile_n; };
+static void gemm_launch(const GemmLaunch& l, hipStream_t s, void** args) {
+    GemmKernel& k = gemm_kernels[l.kern];
+    if (k.lds && !k.attr_done) {
+        hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
         (void)hipGetLastError();
-        attr_set = true;
+        k.attr_done = true;
     }
+    hipLaunchKernel(k.fn, dim3(l.grid), dim3(k.threads), args, k.lds, s);
+}
+
+// ---- route plan -------------------------------------------------------------------------------------------------------------------------
+// One part = one GemmArgs: a GEMM launch over contraction rows [k_off, k_off + K) and, with a workspace split-K, its reduction.  A call is one
+// part, or two for a ragged long weight-gradient contraction.  Everything the route fixes in GemmArgs is spelled out here, zeros included.
+struct GemmPart {
+    GemmLaunch gemm, reduce;
+    int k_off, K;
+    int N, nb_rows;                      // after the c_pad_writable rounding
+    int k_per_split, splits, group_n, dbg, owner, assign;
+    int ws_tiles, rpt;                   // workspace tiles per split and their rows; the reduction's tiles_n is ceil(N / BN)
+    size_t ws_bytes;                     // > 0: the part needs this much split-K workspace
+};
+enum GemmPlanError { GP_OK = 0, GP_E_ROWMAP, GP_E_ASSIGN_SPLITK };
+struct GemmPlan { int err, n_parts; GemmPart part[2]; };
+
+// epilogue feature mask of a call -> index of the smallest instantiated superset
+static int gemm_feature_index(int N, const lav_gemm_epilogue& e) {
+    unsigned fm = 0;
+    if (e.bias) fm |= EF_BIAS;
+    if (e.act == 1 && (!e.preact || e.preact_is_grad)) fm |= EF_ACT;
+    else if (e.act != 0 || e.preact) fm |= EF_GENERIC;
+    if (e.gelu_in) fm |= e.gelu_in_is_grad ? EF_GIN : EF_GENERIC;
+    if (e.dropout_p > 0.f) fm |= EF_DROP;
+    if (e.row_scale) fm |= EF_RSCALE;
+    if (e.residual) fm |= EF_RES;
+    if (e.colsum) fm |= EF_COLSUM;
+    if (e.out_mode == 1 || e.out_mode == 3) fm |= EF_O32;           // EF_O32 = 'not a bf16 store': fp32 or fp16 rows, told apart at run time
+    if (e.out_mode == 2 || (N % 8) != 0) fm |= EF_GENERIC;
+    return !(fm & ~S_B) ? 0 : !(fm & ~S_BG) ? 1 : !(fm & ~S_GC) ? 2 : !(fm & ~S_BDR) ? 3 : ((fm & EF_O32) && !(fm & ~S_BDRO)) ? 4 : FI_ALL;
+}
+// a plain weight-gradient flush: fp32 accumulate, nothing else in the epilogue (alpha, rowsum_a and k_keep are allowed)
+static bool tn_plain(const lav_gemm_epilogue& e) {
+    return e.out_mode == 2 && !e.bias && !e.act && !e.preact && !e.gelu_in && e.dropout_p <= 0.f && !e.row_scale && !e.residual && !e.colsum;
+}
+// rows enough for the 256-row weight-gradient tiles (192 x 768: 324 -> 198 us; 192 x 192: 112 -> 124 us, stays on the small kernel)
+static bool tn_rows_enough(int M, int N, const GemmSwitches& sw) { return M >= (N >= 512 ? sw.tn_min_m : (sw.tn_min_m > 256 ? sw.tn_min_m : 256)); }
+// fits the ping-pong weight-gradient kernel: 256 x 256 tiles, k-tiles of 32, drop-path groups of at least keep_rows rows and at most 128 of them
+static bool tn_pp_fits(int M, int N, int K, const void* k_keep, int k_rows_per_group, int keep_rows, const GemmSwitches& sw) {
+    return sw.pp_tn && sw.tn_kind != 0 && sw.tn_kind != 1 && tn_rows_enough(M, N, sw) && (N % 256) == 0 && (K % PP_BK) == 0 &&
+           (!k_keep || (k_rows_per_group >= keep_rows && (K + k_rows_per_group - 1) / k_rows_per_group <= 128));
+}
+static int gemm_group_n(int N, const GemmSwitches& sw) {
+    const int tn = N / 256;
+    return sw.group_n >= 0 ? sw.group_n : (tn >= 8 && tn % 4 == 0 ? 4 : 0);
+}
+
+static GemmPlanError gemm_plan_part(GemmPart& q, int layout, int M, int N, int k_off, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue& e,
+                                    bool assign, int splits, const GemmSwitches& sw) {
+    const int kps = ((K + splits - 1) / splits + BKT - 1) / BKT * BKT;          // a multiple of BKT, and so of PP_BK
+    splits = (K + kps - 1) / kps;
+    q.gemm = {-1, 0, 0, 0}; q.reduce = {-1, 0, 0, 0};
+    q.k_off = k_off; q.K = K; q.N = N; q.nb_rows = 0;
+    q.k_per_split = kps; q.splits = splits; q.group_n = 0; q.dbg = 0; q.owner = 0; q.assign = assign;
+    q.ws_tiles = 0; q.rpt = 0; q.ws_bytes = 0;
     // ragged N whose padding columns the caller lets us overwrite (the 30522-wide vocabulary projection into its 30528-wide logits
     // buffer): run as N rounded up to 8 so that the 16-byte-chunk epilogues apply (the generic one was 566 vs 256 us for the vendor
     // library on 5120 x 30522 x 768); B rows and bias entries past the real N are never read
-    if (g.e.c_pad_writable && (N % 8) != 0 && layout == 0 && splits == 1 && (K % BKT) == 0 && M >= 2048 && g.e.out_mode == 0 &&
-        ldc >= (long)((N + 7) / 8 * 8) && !g.e.colsum && !g.e.preact && !g.e.gelu_in && !g.e.residual && !g.e.a_rowmap) {
-        g.nb_rows = N;
-        N = (N + 7) / 8 * 8;
-        g.N = N;
+    if (e.c_pad_writable && (N % 8) != 0 && layout == 0 && splits == 1 && (K % BKT) == 0 && M >= 2048 && e.out_mode == 0 &&
+        ldc >= (long)((N + 7) / 8 * 8) && !e.colsum && !e.preact && !e.gelu_in && !e.residual && !e.a_rowmap) {
+        q.nb_rows = N;
+        q.N = N = (N + 7) / 8 * 8;
     }
     const bool big = layout != 2 && splits == 1 && (K % BKT) == 0 && M >= 2048;
-    // epilogue feature mask of this call -> smallest instantiated superset (EF_ALL = the generic code)
-    unsigned fm = 0;
-    if (g.e.bias) fm |= EF_BIAS;
-    if (g.e.act == 1 && (!g.e.preact || g.e.preact_is_grad)) fm |= EF_ACT;
-    else if (g.e.act != 0 || g.e.preact) fm |= EF_GENERIC;
-    if (g.e.gelu_in) fm |= g.e.gelu_in_is_grad ? EF_GIN : EF_GENERIC;
-    if (g.e.dropout_p > 0.f) fm |= EF_DROP;
-    if (g.e.row_scale) fm |= EF_RSCALE;
-    if (g.e.residual) fm |= EF_RES;
-    if (g.e.colsum) fm |= EF_COLSUM;
-    if (g.e.out_mode == 1 || g.e.out_mode == 3) fm |= EF_O32;       // EF_O32 = 'not a bf16 store': fp32 or fp16 rows, told apart at run time
-    if (g.e.out_mode == 2 || (N % 8) != 0) fm |= EF_GENERIC;
-    constexpr unsigned S_B = EF_BIAS, S_BG = EF_BIAS | EF_ACT, S_GC = EF_GIN | EF_RSCALE | EF_COLSUM,
-                       S_BDR = EF_BIAS | EF_DROP | EF_RSCALE | EF_RES, S_BDRO = S_BDR | EF_O32;
-    const unsigned fsel = !(fm & ~S_B) ? S_B : !(fm & ~S_BG) ? S_BG : !(fm & ~S_GC) ? S_GC : !(fm & ~S_BDR) ? S_BDR :
-                          ((fm & EF_O32) && !(fm & ~S_BDRO)) ? S_BDRO : EF_ALL;
-    constexpr int lav_threads_gemm_huge_kernel = 512, lav_threads_gemm_big_kernel = 512, lav_threads_gemm_h192_kernel = 512, lav_threads_gemm_h192l_kernel = 640;
-    (void)lav_threads_gemm_huge_kernel; (void)lav_threads_gemm_big_kernel; (void)lav_threads_gemm_h192_kernel; (void)lav_threads_gemm_h192l_kernel;
-#define LAV_LAUNCH_ONE(KERN, AKC_, BKC_, F_, GRID, LDS)                                                                   \
-    do {                                                                                                                  \
-        static bool attr_done = false;                                                                                    \
-        if (!attr_done) {                                                                                                 \
-            hipFuncSetAttribute((const void*)KERN<AKC_, BKC_, F_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);      \
-            (void)hipGetLastError();                                                                                      \
-            attr_done = true;                                                                                             \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((KERN<AKC_, BKC_, F_>), GRID, dim3(lav_threads_##KERN), LDS, s, g);                            \
-    } while (0)
-#define LAV_LAUNCH_BY_LAYOUT(KERN, F_, GRID, LDS)                                                                         \
-    do {                                                                                                                  \
-        if (layout == 0) LAV_LAUNCH_ONE(KERN, true, true, F_, GRID, LDS);                                                 \
-        else LAV_LAUNCH_ONE(KERN, true, false, F_, GRID, LDS);                                                            \
-    } while (0)
-#define LAV_LAUNCH_BY_FEATURES(KERN, GRID, LDS)                                                                           \
-    do {                                                                                                                  \
-        if (fsel == S_B) LAV_LAUNCH_BY_LAYOUT(KERN, S_B, GRID, LDS);                                                      \
-        else if (fsel == S_BG) LAV_LAUNCH_BY_LAYOUT(KERN, S_BG, GRID, LDS);                                               \
-        else if (fsel == S_GC) LAV_LAUNCH_BY_LAYOUT(KERN, S_GC, GRID, LDS);                                               \
-        else if (fsel == S_BDR) LAV_LAUNCH_BY_LAYOUT(KERN, S_BDR, GRID, LDS);                                             \
-        else if (fsel == S_BDRO) LAV_LAUNCH_BY_LAYOUT(KERN, S_BDRO, GRID, LDS);                                           \
-        else LAV_LAUNCH_BY_LAYOUT(KERN, EF_ALL, GRID, LDS);                                                               \
-    } while (0)
+    const int fi = gemm_feature_index(N, e);
+    const bool small32 = (long)M * lda * 2 < (1L << 31) && (long)N * ldb * 2 < (1L << 31);       // both operands below 2 GiB: what the phase-shifted kernels address
     // pick the tile by estimated machine fill: tiles / (rounds * resident slots), weighted by the tile's own efficiency
     auto fill = [](long tiles, long slots, double w) { return w * (double)tiles / (double)(((tiles + slots - 1) / slots) * slots); };
     const long t_small = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
@@ -1777,157 +1812,187 @@ extern "C" int lav_gemm_bf16(void* stream, int layout, int M, int N, int K, cons
     const long t_huge = (long)((M + BIG_BM - 1) / BIG_BM) * (N / 256);
     constexpr double w_big = 0.80;                            // measured best once the dW stream fills partial rounds (0.88 before)
     const double f_small = fill(t_small, 512, 0.80), f_big = fill(t_big, 256, w_big);
-    const double f_huge = ((N % 256) == 0 && !g.nb_rows) ? fill(t_huge, 256, 1.0) : 0.0;
+    const double f_huge = ((N % 256) == 0 && !q.nb_rows) ? fill(t_huge, 256, 1.0) : 0.0;
     // 192-row tiles where they fill the machine better (narrow outputs: N = 768 at M = 45120 is 2.07 rounds of 256-row tiles)
     const long t_h192 = (long)((M + 191) / 192) * (N / 256);
-    const double f_h192 = ((N % 256) == 0 && fsel != EF_ALL && lav_gemm_h192 && !g.nb_rows) ? fill(t_h192, 256, 0.97) : 0.0;
-#define LAV_PS_(F_, RF_) { static bool ad = false; if (!ad) { hipFuncSetAttribute((const void*)gemm_ps_kernel<F_, RF_>, hipFuncAttributeMaxDynamicSharedMemorySize, HUGE_LDS); (void)hipGetLastError(); ad = true; } \
-                     hipLaunchKernelGGL((gemm_ps_kernel<F_, RF_>), hgrid, dim3(512), HUGE_LDS, s, g); }
-#define LAV_PS(F_) LAV_PS_(F_, 8)
-#define LAV_PS_256() do { if (fsel == S_B) LAV_PS(S_B) else if (fsel == S_BG) LAV_PS(S_BG) else if (fsel == S_GC) LAV_PS(S_GC) else if (fsel == S_BDR) LAV_PS(S_BDR) else LAV_PS(S_BDRO) } while (0)
-    if (g.e.a_rowmap) {                                      // pair-expanded A rows: the 256 x 256 kernel reads them through the map
-        LAV_REQUIRE(layout == 0 && splits == 1 && (N % 256) == 0 && (K % BKT) == 0,
-                    "lav_gemm_bf16: a_rowmap needs layout 0, splits 1, N %% 256 == 0 and K %% 64 == 0 (got layout %d, N %d, K %d)", layout, N, K);
-        g.k_per_split = K;
-        const int tn_ = N / 256;
-        g.group_n = lav_gemm_group_n >= 0 ? lav_gemm_group_n : (tn_ >= 8 && tn_ % 4 == 0 ? 4 : 0);
-        dim3 hgrid((unsigned)t_huge);
-        if ((lav_gemm_ps & 1) && fsel != EF_ALL && (long)M * lda * 2 < (1L << 31) && (long)N * ldb * 2 < (1L << 31)) {      // (M bounds the mapped rows' source too: the map indexes rows of A below the caller's source row count <= M)
-            LAV_PS_256();
-            return lav_check_launch("lav_gemm_bf16");
-        }
-        LAV_LAUNCH_BY_FEATURES(gemm_huge_kernel, hgrid, HUGE_LDS);
-        return lav_check_launch("lav_gemm_bf16");
+    const double f_h192 = ((N % 256) == 0 && fi != FI_ALL && sw.h192 && !q.nb_rows) ? fill(t_h192, 256, 0.97) : 0.0;
+    if (e.a_rowmap) {                                        // pair-expanded A rows: the 256 x 256 kernel reads them through the map
+        if (!(layout == 0 && splits == 1 && (N % 256) == 0 && (K % BKT) == 0)) return GP_E_ROWMAP;
+        q.k_per_split = K;
+        q.group_n = gemm_group_n(N, sw); q.dbg = 0;
+        // (M bounds the mapped rows' source too: the map indexes rows of A below the caller's source row count <= M)
+        q.gemm = {(sw.ps & 1) && fi != FI_ALL && small32 ? GK_PS256 + fi : GK_HUGE + 2 * fi, (unsigned)t_huge, 256, 256};
+        return GP_OK;
     }
     if (big && f_h192 > f_huge + 0.02 && f_h192 >= f_big && f_h192 >= f_small) {
-        g.k_per_split = K;
-        g.dbg = lav_gemm_dbg; g.group_n = 0;
-        dim3 hgrid((unsigned)t_h192);
-        if ((lav_gemm_ps & 2) && layout == 0 && (long)M * lda * 2 < (1L << 31) && (long)N * ldb * 2 < (1L << 31)) {
-#define LAV_PS6(F_) LAV_PS_(F_, 6)
-            if (fsel == S_B) LAV_PS6(S_B) else if (fsel == S_BG) LAV_PS6(S_BG) else if (fsel == S_GC) LAV_PS6(S_GC) else if (fsel == S_BDR) LAV_PS6(S_BDR) else LAV_PS6(S_BDRO)
-#undef LAV_PS6
-            return lav_check_launch("lav_gemm_bf16");
-        }
-#define LAV_H192(F_) { if (layout == 0 && lav_gemm_h192l) LAV_LAUNCH_ONE(gemm_h192l_kernel, true, true, F_, hgrid, HUGE_LDS); else if (layout == 0) LAV_LAUNCH_ONE(gemm_h192_kernel, true, true, F_, hgrid, HUGE_LDS); else LAV_LAUNCH_ONE(gemm_h192_kernel, true, false, F_, hgrid, HUGE_LDS); }
-        if (fsel == S_B) LAV_H192(S_B) else if (fsel == S_BG) LAV_H192(S_BG) else if (fsel == S_GC) LAV_H192(S_GC)
-        else if (fsel == S_BDR) LAV_H192(S_BDR) else LAV_H192(S_BDRO)
-#undef LAV_H192
-        return lav_check_launch("lav_gemm_bf16");
+        q.k_per_split = K;
+        q.group_n = 0; q.dbg = sw.dbg;
+        q.gemm = {(sw.ps & 2) && layout == 0 && small32 ? GK_PS192 + fi : GK_H192 + 3 * fi + (layout == 0 ? (sw.h192l ? 0 : 1) : 2), (unsigned)t_h192, 192, 256};
+        return GP_OK;
     }
     if (big && f_huge >= f_big && f_huge >= f_small) {
-        g.k_per_split = K;
-        dim3 hgrid((unsigned)t_huge);
-        g.dbg = lav_gemm_dbg;
-        if (layout != 2) {
-            const int tn_ = N / 256;
-            g.group_n = lav_gemm_group_n >= 0 ? lav_gemm_group_n : (tn_ >= 8 && tn_ % 4 == 0 ? 4 : 0);
-        }
-        if ((lav_gemm_ps & 1) && layout == 0 && fsel != EF_ALL && (long)M * lda * 2 < (1L << 31) && (long)N * ldb * 2 < (1L << 31)) {
-            LAV_PS_256();
-            return lav_check_launch("lav_gemm_bf16");
-        }
-        LAV_LAUNCH_BY_FEATURES(gemm_huge_kernel, hgrid, HUGE_LDS);
-        return lav_check_launch("lav_gemm_bf16");
+        q.k_per_split = K;
+        q.group_n = gemm_group_n(N, sw); q.dbg = sw.dbg;
+        q.gemm = {(sw.ps & 1) && layout == 0 && fi != FI_ALL && small32 ? GK_PS256 + fi : GK_HUGE + 2 * fi + layout, (unsigned)t_huge, 256, 256};
+        return GP_OK;
     }
-    if (big && (f_big >= f_small || g.nb_rows)) {
-        dim3 bgrid(((M + BIG_BM - 1) / BIG_BM) * ((N + BN - 1) / BN));
-        g.k_per_split = K;
-        LAV_LAUNCH_BY_FEATURES(gemm_big_kernel, bgrid, BIG_LDS);
-        return lav_check_launch("lav_gemm_bf16");
+    if (big && (f_big >= f_small || q.nb_rows)) {
+        q.k_per_split = K;
+        q.group_n = 0; q.dbg = 0;
+        q.gemm = {GK_BIG + 2 * fi + layout, (unsigned)t_big, 256, 128};
+        return GP_OK;
     }
     if (layout != 2) {
-        const bool sk = splits > 1 && g.e.out_mode == 0;     // under-filled long-K problem (vocabulary contraction): workspace split-K
-        const bool sk_huge = sk && (K % BKT) == 0 && (kps % BKT) == 0 && M >= 256 && (N % 256) == 0;
-        const int rpt = sk_huge ? BIG_BM : BM;
-        const int ws_tiles = ((M + rpt - 1) / rpt) * ((N + BN - 1) / BN);
+        const bool sk = splits > 1 && e.out_mode == 0;       // under-filled long-K problem (vocabulary contraction): workspace split-K
+        const bool sk_huge = sk && (K % BKT) == 0 && M >= 256 && (N % 256) == 0;
+        q.group_n = 0; q.dbg = 0;
+        if (sk_huge) q.gemm = {GK_HUGE + 2 * FI_ALL + layout, (unsigned)(t_huge * splits), 256, 256};
+        else q.gemm = {GK_SMALL + layout, (unsigned)(t_small * splits), 128, 128};
         if (sk) {
-            g.ws = splitk_workspace(stream, (size_t)splits * ws_tiles * rpt * BN * sizeof(float));
-            if (!g.ws) return LAV_E_WORKSPACE;               // message set by lav_ws_get
-            g.ws_tiles = ws_tiles;
+            q.rpt = sk_huge ? BIG_BM : BM;
+            q.ws_tiles = ((M + q.rpt - 1) / q.rpt) * ((N + BN - 1) / BN);
+            q.ws_bytes = (size_t)splits * q.ws_tiles * q.rpt * BN * sizeof(float);
+            q.reduce = {GK_SPLITK_REDUCE, (unsigned)(((long)M * (N / 8) + 255) / 256), q.gemm.tile_m, q.gemm.tile_n};
         }
-        if (sk_huge) {
-            const dim3 hg((unsigned)(((M + BIG_BM - 1) / BIG_BM) * (N / 256) * splits));
-            if (layout == 0) LAV_LAUNCH_ONE(gemm_huge_kernel, true, true, EF_ALL, hg, HUGE_LDS);
-            else LAV_LAUNCH_ONE(gemm_huge_kernel, true, false, EF_ALL, hg, HUGE_LDS);
-        } else if (layout == 0) hipLaunchKernelGGL((gemm_kernel<true, true, 1>), grid, block, GEMM_LDS_BYTES, s, g);
-        else hipLaunchKernelGGL((gemm_kernel<true, false, 1>), grid, block, GEMM_LDS_BYTES, s, g);
-        if (sk) {
-            const long n = (long)M * (N / 8);
-            hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g.ws, splits, ws_tiles,
-                               (N + BN - 1) / BN, rpt, M, N, (bf16_t*)C, ldc);
-        }
-    } else {
-        // ---- weight gradients -------------------------------------------------------------------------------------
-        // flush (out_mode 2): one block per output tile -> plain read-modify-write; split-K -> private partial tiles in a
-        // workspace + one reduction pass.  fp32 atomics only remain for ragged N.
-        const bool plain = g.e.out_mode == 2 && !g.e.bias && !g.e.act && !g.e.preact && !g.e.gelu_in && g.e.dropout_p <= 0.f &&
-                           !g.e.row_scale && !g.e.residual && !g.e.colsum;
-        // A long contraction that is not a multiple of the k-tile (the fusion encoder's token rows n * L: 30280 at cfg4, 33840 at the
-        // reference's shipped batch of 24) used to drop the whole weight gradient onto the 128 x 128 kernel (18 ms per cfg4 step on the
-        // weight-gradient stream).  Split it instead: the first K - K % 64 rows on the large-tile kernels, the < 64-row tail on the small one;
-        // both accumulate into C on this stream (alpha, rowsum_a apply to both parts).
-        // outputs with 160 ... 255 rows (Swin-L stage 0: C = 192) also take the 256-row tiles (a quarter of the tile idle, still well ahead of the
-        // 128 x 128 kernel); LAV_GEMM_TN_MINM=256 restores the old threshold
-        static const int tn_min_m_env = getenv("LAV_GEMM_TN_MINM") ? atoi(getenv("LAV_GEMM_TN_MINM")) : 160;
-        const int tn_min_m = N >= 512 ? tn_min_m_env : (tn_min_m_env > 256 ? tn_min_m_env : 256);      // 192 x 768: 324 -> 198 us; 192 x 192: 112 -> 124 us (stays on the small kernel)
-        if (plain && !g.e.k_keep && M >= tn_min_m && K >= 2048 && (K % PP_BK) != 0 && lav_gemm_tn_kind != 0) {
-            const int K0 = K / BKT * BKT;
-            const int rc0 = lav_gemm_bf16(stream, 2, M, N, K0, A, lda, B, ldb, C, ldc, epi, splits);
-            if (rc0 != LAV_OK) return rc0;
-            lav_gemm_epilogue tail = *epi;                   // (plain => epi != NULL: out_mode 2)
-            tail.assign = 0;                                 // the first part assigned (or accumulated); the tail always accumulates
-            return lav_gemm_bf16(stream, 2, M, N, K - K0, (const bf16_t*)A + (long)K0 * lda, lda, (const bf16_t*)B + (long)K0 * ldb, ldb, C, ldc, &tail, 1);
-        }
-        int kind = 0;                                        // 0: 128x128 two-group kernel, 1: 256x128, 2: 256x256
-        const bool large_ok = plain && (K % BKT) == 0 && (kps % BKT) == 0 && M >= tn_min_m &&
-                              (!g.e.k_keep || g.e.k_rows_per_group >= BKT);
-        if (large_ok && lav_gemm_tn_kind != 0) kind = (N % 256) == 0 && lav_gemm_tn_kind != 1 ? 2 : 1;
-        // contraction lengths that are multiples of 32 but not of 64 (Swin stage 3: 7840 token rows): the ping-pong kernel walks k-tiles of 32
-        // (k_per_split is a multiple of 64, so only the last split ends on a 32-boundary) -- before round 4 these fell to the 128 x 128 kernel
-        const bool pp_only = !large_ok && plain && (K % PP_BK) == 0 && (K % BKT) != 0 && M >= tn_min_m && (N % 256) == 0 &&
-                             lav_gemm_pp_tn && lav_gemm_tn_kind != 0 && lav_gemm_tn_kind != 1 &&
-                             (!g.e.k_keep || (g.e.k_rows_per_group >= BKT && (K + g.e.k_rows_per_group - 1) / g.e.k_rows_per_group <= 128));
-        if (pp_only) kind = 2;
-        const int rpt = kind ? BIG_BM : BM;
-        const int ws_tiles = ((M + rpt - 1) / rpt) * ((N + BN - 1) / BN);
-        bool reduce = false;
-        if (g.e.out_mode == 2) {
-            if (splits == 1) g.owner = 1;
-            else if ((N % 4) == 0 && (ldc % 4) == 0) {
-                float* ws = splitk_workspace(stream, (size_t)splits * ws_tiles * rpt * BN * sizeof(float));
-                if (!ws) return LAV_E_WORKSPACE;             // message set by lav_ws_get
-                g.ws = ws; g.ws_tiles = ws_tiles; reduce = true;
-            }
-            LAV_REQUIRE(!g.assign || g.owner || reduce, "lav_gemm_bf16: assign with split-K needs N %% 4 == 0 and ldc %% 4 == 0 (got N %d, ldc %ld)", N, ldc);
-        }
-        if (kind == 2 && lav_gemm_pp_tn && (K % PP_BK) == 0 && (kps % PP_BK) == 0 &&
-            (!g.e.k_keep || (g.e.k_rows_per_group >= PP_BK && (K + g.e.k_rows_per_group - 1) / g.e.k_rows_per_group <= 128))) {
-            static bool a3 = false;
-            if (!a3) { hipFuncSetAttribute((const void*)gemm_pp_kernel<true, EF_TNFLUSH>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS); (void)hipGetLastError(); a3 = true; }
-            hipLaunchKernelGGL((gemm_pp_kernel<true, EF_TNFLUSH>), dim3(((M + BIG_BM - 1) / BIG_BM) * (N / 256) * splits), dim3(512), PP_LDS, s, g);
-        } else if (kind == 2) {
-            static bool a2 = false;
-            if (!a2) { hipFuncSetAttribute((const void*)gemm_huge_kernel<false, false, EF_TNFLUSH>, hipFuncAttributeMaxDynamicSharedMemorySize, HUGE_LDS); (void)hipGetLastError(); a2 = true; }
-            hipLaunchKernelGGL((gemm_huge_kernel<false, false, EF_TNFLUSH>), dim3(((M + BIG_BM - 1) / BIG_BM) * (N / 256) * splits), dim3(512), HUGE_LDS, s, g);
-        } else if (kind == 1) {
-            static bool a1 = false;
-            if (!a1) { hipFuncSetAttribute((const void*)gemm_big_kernel<false, false, EF_TNFLUSH>, hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS); (void)hipGetLastError(); a1 = true; }
-            hipLaunchKernelGGL((gemm_big_kernel<false, false, EF_TNFLUSH>), dim3(ws_tiles * splits), dim3(512), BIG_LDS, s, g);
-        } else if (plain) {
-            static bool a0 = false;
-            if (!a0) { hipFuncSetAttribute((const void*)gemm_kernel<false, false, 2, EF_TNFLUSH>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072); (void)hipGetLastError(); a0 = true; }
-            hipLaunchKernelGGL((gemm_kernel<false, false, 2, EF_TNFLUSH>), grid, dim3(NT_ * 2), 131072, s, g);
-        } else {
-            hipLaunchKernelGGL((gemm_kernel<false, false, 2>), grid, dim3(NT_ * 2), 131072, s, g);
-        }
-        if (reduce) {
-            const long n = (long)M * (N / 4);
-            hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, g.ws, splits, ws_tiles,
-                               (N + BN - 1) / BN, rpt, M, N, (float*)C, ldc, g.assign);
-        }
+        return GP_OK;
     }
-    return lav_check_launch("lav_gemm_bf16");
+    // ---- weight gradients ---------------------------------------------------------------------------------------------------------------
+    // flush (out_mode 2): one block per output tile -> plain read-modify-write; split-K -> private partial tiles in a
+    // workspace + one reduction pass.  fp32 atomics only remain for ragged N.
+    const bool plain = tn_plain(e);
+    int kind = 0;                                            // 0: 128x128 two-group kernel, 1: 256x128, 2: 256x256
+    const bool large_ok = plain && (K % BKT) == 0 && tn_rows_enough(M, N, sw) && (!e.k_keep || e.k_rows_per_group >= BKT);
+    if (large_ok && sw.tn_kind != 0) kind = (N % 256) == 0 && sw.tn_kind != 1 ? 2 : 1;
+    // contraction lengths that are multiples of 32 but not of 64 (Swin stage 3: 7840 token rows): the ping-pong kernel walks k-tiles of 32
+    // (k_per_split is a multiple of 64, so only the last split ends on a 32-boundary) -- before round 4 these fell to the 128 x 128 kernel
+    if (!large_ok && plain && (K % BKT) != 0 && tn_pp_fits(M, N, K, e.k_keep, e.k_rows_per_group, BKT, sw)) kind = 2;
+    q.group_n = 0; q.dbg = 0;
+    q.rpt = kind ? BIG_BM : BM;
+    const int ws_tiles = ((M + q.rpt - 1) / q.rpt) * ((N + BN - 1) / BN);
+    if (e.out_mode == 2) {
+        if (splits == 1) q.owner = 1;
+        else if ((N % 4) == 0 && (ldc % 4) == 0) {
+            q.ws_tiles = ws_tiles;
+            q.ws_bytes = (size_t)splits * ws_tiles * q.rpt * BN * sizeof(float);
+            q.reduce = {GK_TN_REDUCE, (unsigned)(((long)M * (N / 4) + 63) / 64), q.rpt, BN};
+        }
+        if (assign && !q.owner && !q.ws_bytes) return GP_E_ASSIGN_SPLITK;
+    }
+    if (kind == 2) q.gemm = {tn_pp_fits(M, N, K, e.k_keep, e.k_rows_per_group, PP_BK, sw) ? GK_PP_TN : GK_HUGE_TN, (unsigned)(t_huge * splits), 256, 256};
+    else if (kind == 1) q.gemm = {GK_BIG_TN, (unsigned)(ws_tiles * splits), 256, 128};
+    else q.gemm = {plain ? GK_SMALL_TN : GK_SMALL + 2, (unsigned)(t_small * splits), 128, 128};
+    return GP_OK;
+}
+
+// The route of one (validated) lav_gemm_bf16 call.  Pure: no HIP call, no workspace, no process state -- the switches come in as an argument.
+// e is the call's epilogue with the defaults filled in (gemm_check_args); its pointers are only tested for presence.
+static GemmPlan gemm_plan(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue& e, int splits, const GemmSwitches& sw) {
+    GemmPlan p;
+    // A long weight-gradient contraction that is not a multiple of the k-tile (the fusion encoder's token rows n * L: 30280 at cfg4, 33840 at the
+    // reference's shipped batch of 24) used to drop the whole weight gradient onto the 128 x 128 kernel (18 ms per cfg4 step on the
+    // weight-gradient stream).  Split it instead: the first K - K % 64 rows on the large-tile kernels (with the call's split factor, clamped to what
+    // the whole K allows), the < 64-row tail on the small one; both accumulate into C on the same stream (alpha, rowsum_a apply to both parts);
+    // the first part assigns when the call does, the tail always accumulates.
+    if (layout == 2 && tn_plain(e) && !e.k_keep && tn_rows_enough(M, N, sw) && K >= 2048 && (K % PP_BK) != 0 && sw.tn_kind != 0) {
+        const int K0 = K / BKT * BKT, kps = ((K + splits - 1) / splits + BKT - 1) / BKT * BKT;
+        p.n_parts = 2;
+        p.err = gemm_plan_part(p.part[0], layout, M, N, 0, K0, lda, ldb, ldc, e, e.assign != 0, (K + kps - 1) / kps, sw);
+        if (!p.err) p.err = gemm_plan_part(p.part[1], layout, M, N, K0, K - K0, lda, ldb, ldc, e, false, 1, sw);
+        return p;
+    }
+    p.n_parts = 1;
+    p.err = gemm_plan_part(p.part[0], layout, M, N, 0, K, lda, ldb, ldc, e, e.assign != 0, splits, sw);
+    return p;
+}
+
+// ---- entries ----------------------------------------------------------------------------------------------------------------------------
+// the argument checks of lav_gemm_bf16 (lav_gemm_plan runs them without operand pointers); fills e and splits with the defaults applied
+static int gemm_check_args(int layout, int M, int N, int K, bool with_operands, const void* A, long lda, const void* B, long ldb, const void* C, long ldc,
+                           const lav_gemm_epilogue* epi, lav_gemm_epilogue& e, int& splits) {
+    LAV_REQUIRE(M > 0 && N > 0 && K > 0, "lav_gemm_bf16: empty problem M=%d N=%d K=%d", M, N, K);
+    LAV_REQUIRE(layout >= 0 && layout <= 2, "lav_gemm_bf16: bad layout %d", layout);
+    LAV_REQUIRE(!with_operands || (A && B && C), "lav_gemm_bf16: null operand");
+    LAV_REQUIRE((lda % 8) == 0 && (ldb % 8) == 0, "lav_gemm_bf16: lda/ldb must be multiples of 8 (16-byte rows)");
+    LAV_REQUIRE(!with_operands || (((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)C % 16) == 0),
+                "lav_gemm_bf16: operands must be 16-byte aligned");
+    if (epi) e = *epi; else { memset(&e, 0, sizeof(e)); e.alpha = 1.f; }
+    LAV_REQUIRE(!e.assign || (layout == 2 && e.out_mode == 2), "lav_gemm_bf16: assign is defined for weight gradients only (layout 2, out_mode 2)");
+    if (e.alpha == 0.f) e.alpha = 1.f;
+    if (splits < 1) splits = 1;
+    LAV_REQUIRE(!e.rowsum_a || layout == 2, "lav_gemm_bf16: rowsum_a is only defined for layout 2 (TN)");
+    const bool no_epilogue = !e.bias && !e.act && !e.preact && !e.gelu_in && e.dropout_p <= 0.f && !e.row_scale &&
+                             !e.residual && !e.colsum && !e.rowsum_a && e.alpha == 1.f;
+    LAV_REQUIRE(splits == 1 || e.out_mode == 2 || (e.out_mode == 0 && layout != 2 && no_epilogue && (N % 8) == 0),
+                "lav_gemm_bf16: split-K needs out_mode=2 (fp32 accumulate), or a bf16 output without epilogue and N %% 8 == 0");
+    LAV_REQUIRE(e.out_mode != 0 || (ldc % 8) == 0, "lav_gemm_bf16: bf16 output needs ldc %% 8 == 0");
+    LAV_REQUIRE(e.hm_heads <= 0 || (e.out_mode == 0 && layout != 2 && splits == 1 && e.hm_head_dim > 0 && (e.hm_head_dim % 8) == 0 &&
+                                    (N % (e.hm_heads * e.hm_head_dim)) == 0 && e.hm_rows >= M),
+                "lav_gemm_bf16: head-major store needs a bf16 output, layout 0 / 1, no split-K, hm_head_dim %% 8 == 0, N %% (hm_heads * hm_head_dim) == 0 and hm_rows >= M");
+    LAV_REQUIRE(e.out_mode == 0 || e.out_mode == 3 || (ldc % 4) == 0, "lav_gemm_bf16: fp32 output needs ldc %% 4 == 0");
+    LAV_REQUIRE(e.out_mode != 3 || ((ldc % 8) == 0 && layout != 2 && splits == 1), "lav_gemm_bf16: fp16 output needs ldc %% 8 == 0, layout 0 / 1, no split-K");
+    return LAV_OK;
+}
+// the two checks that depend on the route
+static int gemm_plan_error(const GemmPlan& p, int layout, int N, int K, long ldc) {
+    LAV_REQUIRE(p.err != GP_E_ROWMAP, "lav_gemm_bf16: a_rowmap needs layout 0, splits 1, N %% 256 == 0 and K %% 64 == 0 (got layout %d, N %d, K %d)", layout, N, K);
+    LAV_REQUIRE(p.err != GP_E_ASSIGN_SPLITK, "lav_gemm_bf16: assign with split-K needs N %% 4 == 0 and ldc %% 4 == 0 (got N %d, ldc %ld)", N, ldc);
+    return LAV_OK;
+}
+
+extern "C" int lav_gemm_bf16(void* stream, int layout, int M, int N, int K, const void* A, long lda, const void* B,
+                             long ldb, void* C, long ldc, const lav_gemm_epilogue* epi, int splits) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    if (int rc = gemm_check_args(layout, M, N, K, true, A, lda, B, ldb, C, ldc, epi, g.e, splits)) return rc;
+    const GemmPlan p = gemm_plan(layout, M, N, K, lda, ldb, ldc, g.e, splits, gemm_sw);
+    if (int rc = gemm_plan_error(p, layout, N, K, ldc)) return rc;
+    g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M;
+    g.drop_thresh = lav_drop_thresh(g.e.dropout_p);
+    g.nt_preact = (gemm_sw.nt_stores & 1) | ((gemm_sw.nt_stores & 4) ? 2 : 0);
+    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < p.n_parts; ++i) {
+        const GemmPart& q = p.part[i];
+        g.A = (const bf16_t*)A + (long)q.k_off * lda; g.B = (const bf16_t*)B + (long)q.k_off * ldb;      // (k_off > 0: weight gradients, both operands [K, ld])
+        g.N = q.N; g.K = q.K; g.nb_rows = q.nb_rows; g.k_per_split = q.k_per_split; g.splits = q.splits; g.group_n = q.group_n; g.dbg = q.dbg;
+        g.owner = q.owner; g.assign = q.assign; g.ws_tiles = q.ws_tiles;          // (the kernels read GemmArgs.assign, never e.assign)
+        g.ws = nullptr;
+        if (q.ws_bytes) {
+            g.ws = splitk_workspace(stream, q.ws_bytes);
+            if (!g.ws) return LAV_E_WORKSPACE;               // message set by lav_ws_get
+        }
+        void* ga[] = {&g};
+        gemm_launch(q.gemm, s, ga);
+        if (q.reduce.kern >= 0) {                            // splitk_reduce_bf16_kernel takes the first nine of these, tn_reduce_kernel all ten
+            int tiles_n = (q.N + BN - 1) / BN, rpt = q.rpt;
+            void* ra[] = {&g.ws, &g.splits, &g.ws_tiles, &tiles_n, &rpt, &g.M, &g.N, &g.C, &g.ldc, &g.assign};
+            gemm_launch(q.reduce, s, ra);
+        }
+        if (int rc = lav_check_launch("lav_gemm_bf16")) return rc;
+    }
+    return LAV_OK;
+}
+
+static void plan_report(const GemmLaunch& l, lav_gemm_launch_info* out, int max_out, int& n) {
+    if (l.kern < 0) return;
+    if (n < max_out) out[n] = {gemm_kernels[l.kern].name, l.tile_m, l.tile_n, l.grid, (unsigned)gemm_kernels[l.kern].threads};
+    ++n;
+}
+static int gemm_plan_query(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits,
+                           lav_gemm_launch_info* out, int max_out, int& n) {
+    lav_gemm_epilogue e;
+    if (int rc = gemm_check_args(layout, M, N, K, false, nullptr, lda, nullptr, ldb, nullptr, ldc, epi, e, splits)) return rc;
+    const GemmPlan p = gemm_plan(layout, M, N, K, lda, ldb, ldc, e, splits, gemm_sw);
+    if (int rc = gemm_plan_error(p, layout, N, K, ldc)) return rc;
+    for (int i = 0; i < p.n_parts; ++i) { plan_report(p.part[i].gemm, out, max_out, n); plan_report(p.part[i].reduce, out, max_out, n); }
+    return LAV_OK;
+}
+// probe hook: the launches lav_gemm_bf16 would make for this call, without making them (no device needed)
+extern "C" int lav_gemm_plan(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits,
+                             lav_gemm_launch_info* out, int max_out) {
+    LAV_REQUIRE(out || max_out <= 0, "lav_gemm_plan: null output array");
+    int n = 0;
+    if (int rc = gemm_plan_query(layout, M, N, K, lda, ldb, ldc, epi, splits, out, max_out, n)) return rc;
+    return n;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1935,77 +2000,110 @@ extern "C" int lav_gemm_bf16(void* stream, int layout, int M, int N, int K, cons
 // Every job must fit that kernel (>= 160 output rows (256 below 512 columns), N % 256 == 0, K % 32 == 0, the drop-path row rule);
 // otherwise -- or with LAV_GEMM_TN_GROUP=0 -- the jobs run one by one through lav_gemm_bf16 with their own fallback split factors.
 // ---------------------------------------------------------------------------------------------------------------------------------
-extern "C" int lav_gemm_tn_grouped(void* stream, int n_jobs, const lav_gemm_tn_job* jobs, int splits) {
-    LAV_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= 4, "lav_gemm_tn_grouped: 1 ... 4 jobs (got %d)", n_jobs);
-    static const bool group_on = getenv("LAV_GEMM_TN_GROUP") ? atoi(getenv("LAV_GEMM_TN_GROUP")) != 0 : true;
-    static const int tn_min_m_env = getenv("LAV_GEMM_TN_MINM") ? atoi(getenv("LAV_GEMM_TN_MINM")) : 160;
-    if (splits < 1) splits = 1;
-    bool ok = group_on && lav_gemm_pp_tn && lav_gemm_tn_kind != 0 && lav_gemm_tn_kind != 1;
+static lav_gemm_epilogue tn_job_epilogue(const lav_gemm_tn_job& q) {          // the job as a lav_gemm_bf16 (layout 2) epilogue
+    lav_gemm_epilogue e;
+    memset(&e, 0, sizeof(e));
+    e.alpha = q.alpha == 0.f ? 1.f : q.alpha; e.rows_per_group = 1; e.out_mode = 2; e.rowsum_a = q.rowsum_a; e.k_keep = q.k_keep;
+    e.k_rows_per_group = q.k_keep ? q.k_rows_per_group : 1;
+    e.assign = q.assign;
+    return e;
+}
+static bool tn_group_fits(int n_jobs, const lav_gemm_tn_job* jobs, bool with_operands, const GemmSwitches& sw) {
+    bool ok = sw.tn_group != 0;
     for (int j = 0; j < n_jobs && ok; ++j) {
         const lav_gemm_tn_job& q = jobs[j];
-        const int tn_min_m = q.N >= 512 ? tn_min_m_env : (tn_min_m_env > 256 ? tn_min_m_env : 256);
-        ok = q.A && q.B && q.C && q.M >= tn_min_m && q.N > 0 && (q.N % 256) == 0 && q.K >= PP_BK && (q.K % PP_BK) == 0 && (q.lda % 8) == 0 && (q.ldb % 8) == 0 &&
-             (q.ldc % 4) == 0 && (((uintptr_t)q.A | (uintptr_t)q.B | (uintptr_t)q.C) & 15) == 0 &&
-             (!q.k_keep || (q.k_rows_per_group >= BKT && (q.K + q.k_rows_per_group - 1) / q.k_rows_per_group <= 128));
+        ok = (!with_operands || (q.A && q.B && q.C && (((uintptr_t)q.A | (uintptr_t)q.B | (uintptr_t)q.C) & 15) == 0)) && q.N > 0 && q.K >= PP_BK &&
+             (q.lda % 8) == 0 && (q.ldb % 8) == 0 && (q.ldc % 4) == 0 && tn_pp_fits(q.M, q.N, q.K, q.k_keep, q.k_rows_per_group, BKT, sw);
     }
-    if (!ok) {
+    return ok;
+}
+// the grouped launch: per job its split (at least 256 contraction rows each), workspace slice and first block, and the blocks of the two launches
+struct TnGroupPlan { int k_per_split[4], splits[4], ws_tiles[4], blk0[4], rblk0[4], blocks, rblocks; size_t ws_off[4], ws_bytes; };
+static TnGroupPlan tn_group_plan(int n_jobs, const lav_gemm_tn_job* jobs, int splits) {
+    TnGroupPlan p;
+    memset(&p, 0, sizeof(p));
+    for (int j = 0; j < n_jobs; ++j) {
+        const lav_gemm_tn_job& q = jobs[j];
+        int sp = splits;
+        if (sp > q.K / 256) sp = q.K / 256 > 0 ? q.K / 256 : 1;
+        p.k_per_split[j] = ((q.K + sp - 1) / sp + BKT - 1) / BKT * BKT;
+        p.splits[j] = (q.K + p.k_per_split[j] - 1) / p.k_per_split[j];
+        p.ws_tiles[j] = ((q.M + BIG_BM - 1) / BIG_BM) * ((q.N + BN - 1) / BN);
+        p.blk0[j] = p.blocks;
+        p.blocks += ((q.M + BIG_BM - 1) / BIG_BM) * (q.N / 256) * p.splits[j];
+        if (p.splits[j] > 1) {
+            p.ws_off[j] = p.ws_bytes;
+            p.ws_bytes += (size_t)p.splits[j] * p.ws_tiles[j] * BIG_BM * BN * sizeof(float);
+            p.rblk0[j] = p.rblocks;
+            p.rblocks += (int)(((long)q.M * (q.N / 4) + 63) / 64);
+        }
+    }
+    return p;
+}
+
+extern "C" int lav_gemm_tn_grouped(void* stream, int n_jobs, const lav_gemm_tn_job* jobs, int splits) {
+    LAV_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= 4, "lav_gemm_tn_grouped: 1 ... 4 jobs (got %d)", n_jobs);
+    if (splits < 1) splits = 1;
+    if (!tn_group_fits(n_jobs, jobs, true, gemm_sw)) {
         for (int j = 0; j < n_jobs; ++j) {
             const lav_gemm_tn_job& q = jobs[j];
-            lav_gemm_epilogue e;
-            memset(&e, 0, sizeof(e));
-            e.alpha = q.alpha == 0.f ? 1.f : q.alpha; e.rows_per_group = 1; e.out_mode = 2; e.rowsum_a = q.rowsum_a; e.k_keep = q.k_keep;
-            e.k_rows_per_group = q.k_keep ? q.k_rows_per_group : 1;
-            e.assign = q.assign;
+            const lav_gemm_epilogue e = tn_job_epilogue(q);
             if (int rc = lav_gemm_bf16(stream, 2, q.M, q.N, q.K, q.A, q.lda, q.B, q.ldb, q.C, q.ldc, &e, q.fallback_splits > 0 ? q.fallback_splits : 1)) return rc;
         }
         return LAV_OK;
     }
+    const TnGroupPlan p = tn_group_plan(n_jobs, jobs, splits);
+    float* ws = nullptr;
+    if (p.ws_bytes) {
+        ws = splitk_workspace(stream, p.ws_bytes);
+        if (!ws) return LAV_E_WORKSPACE;                     // message set by lav_ws_get
+    }
     GemmGroup G;
+    TnReduceGroup R;
     memset(&G, 0, sizeof(G));
+    memset(&R, 0, sizeof(R));
     G.n = n_jobs;
     G.walk = 3;                                              // launch-wide XCD runs, short-dimension-fastest tiles (profiles/r05_dw_walk.md; 0 = the round-4 walk)
-    size_t ws_off[4] = {0, 0, 0, 0}, ws_bytes = 0;
-    int ws_tiles[4] = {0, 0, 0, 0}, blocks = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const lav_gemm_tn_job& q = jobs[j];
         GemmArgs& g = G.g[j];
         g.A = (const bf16_t*)q.A; g.B = (const bf16_t*)q.B; g.C = q.C; g.lda = q.lda; g.ldb = q.ldb; g.ldc = q.ldc; g.M = q.M; g.N = q.N; g.K = q.K;
-        g.e.alpha = q.alpha == 0.f ? 1.f : q.alpha; g.e.rows_per_group = 1; g.e.out_mode = 2; g.e.rowsum_a = q.rowsum_a; g.e.k_keep = q.k_keep;
-        g.e.k_rows_per_group = q.k_keep ? q.k_rows_per_group : 1;
+        g.e = tn_job_epilogue(q);
+        g.e.assign = 0;                                      // (the kernels read GemmArgs.assign)
         g.assign = q.assign != 0;
-        int sp = splits;
-        if (sp > q.K / 256) sp = q.K / 256 > 0 ? q.K / 256 : 1;
-        const int kps = ((q.K + sp - 1) / sp + BKT - 1) / BKT * BKT;
-        g.k_per_split = kps;
-        g.splits = (q.K + kps - 1) / kps;
-        ws_tiles[j] = ((q.M + BIG_BM - 1) / BIG_BM) * ((q.N + BN - 1) / BN);
-        if (g.splits == 1) g.owner = 1;
-        else { ws_off[j] = ws_bytes; ws_bytes += (size_t)g.splits * ws_tiles[j] * BIG_BM * BN * sizeof(float); }
-        G.blk0[j] = blocks;
-        blocks += ((q.M + BIG_BM - 1) / BIG_BM) * (q.N / 256) * g.splits;
-    }
-    if (ws_bytes) {
-        float* ws = splitk_workspace(stream, ws_bytes);
-        if (!ws) return LAV_E_WORKSPACE;                     // message set by lav_ws_get
-        for (int j = 0; j < n_jobs; ++j)
-            if (G.g[j].splits > 1) { G.g[j].ws = (float*)((char*)ws + ws_off[j]); G.g[j].ws_tiles = ws_tiles[j]; }
+        g.k_per_split = p.k_per_split[j];
+        g.splits = p.splits[j];
+        G.blk0[j] = p.blk0[j];
+        if (g.splits == 1) { g.owner = 1; continue; }
+        g.ws = (float*)((char*)ws + p.ws_off[j]); g.ws_tiles = p.ws_tiles[j];
+        TnReduceJob& r = R.j[R.n++];
+        r.ws = g.ws; r.C = (float*)g.C; r.ldc = g.ldc; r.splits = g.splits; r.tiles = p.ws_tiles[j]; r.tiles_n = (g.N + BN - 1) / BN; r.rpt = BIG_BM; r.M = g.M; r.N = g.N;
+        r.blk0 = p.rblk0[j]; r.assign = g.assign;
     }
     hipStream_t s = (hipStream_t)stream;
-    static bool attr = false;
-    if (!attr) { hipFuncSetAttribute((const void*)gemm_pp_group_kernel<true, EF_TNFLUSH>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS); (void)hipGetLastError(); attr = true; }
-    hipLaunchKernelGGL((gemm_pp_group_kernel<true, EF_TNFLUSH>), dim3(blocks), dim3(512), PP_LDS, s, G);
-    TnReduceGroup R;
-    memset(&R, 0, sizeof(R));
-    int rblocks = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const GemmArgs& g = G.g[j];
-        if (g.splits > 1) {
-            TnReduceJob& q = R.j[R.n++];
-            q.ws = g.ws; q.C = (float*)g.C; q.ldc = g.ldc; q.splits = g.splits; q.tiles = ws_tiles[j]; q.tiles_n = (g.N + BN - 1) / BN; q.rpt = BIG_BM; q.M = g.M; q.N = g.N;
-            q.blk0 = rblocks; q.assign = g.assign;
-            rblocks += (int)(((long)g.M * (g.N / 4) + 63) / 64);
-        }
-    }
-    if (R.n) hipLaunchKernelGGL(tn_reduce_group_kernel, dim3(rblocks), dim3(256), 0, s, R);
+    void* ga[] = {&G};
+    gemm_launch({GK_PP_GROUP, (unsigned)p.blocks, 256, 256}, s, ga);
+    void* ra[] = {&R};
+    if (R.n) gemm_launch({GK_TN_REDUCE_GROUP, (unsigned)p.rblocks, 256, BN}, s, ra);
     return lav_check_launch("lav_gemm_tn_grouped");
+}
+
+// probe hook: the launches lav_gemm_tn_grouped would make (one grouped launch, or the job-by-job fallback), without making them
+extern "C" int lav_gemm_tn_grouped_plan(int n_jobs, const lav_gemm_tn_job* jobs, int splits, lav_gemm_launch_info* out, int max_out) {
+    LAV_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= 4, "lav_gemm_tn_grouped: 1 ... 4 jobs (got %d)", n_jobs);
+    LAV_REQUIRE(out || max_out <= 0, "lav_gemm_tn_grouped_plan: null output array");
+    if (splits < 1) splits = 1;
+    int n = 0;
+    if (!tn_group_fits(n_jobs, jobs, false, gemm_sw)) {
+        for (int j = 0; j < n_jobs; ++j) {
+            const lav_gemm_tn_job& q = jobs[j];
+            const lav_gemm_epilogue e = tn_job_epilogue(q);
+            if (int rc = gemm_plan_query(2, q.M, q.N, q.K, q.lda, q.ldb, q.ldc, &e, q.fallback_splits > 0 ? q.fallback_splits : 1, out, max_out, n)) return rc;
+        }
+        return n;
+    }
+    const TnGroupPlan p = tn_group_plan(n_jobs, jobs, splits);
+    plan_report({GK_PP_GROUP, (unsigned)p.blocks, 256, 256}, out, max_out, n);
+    if (p.rblocks) plan_report({GK_TN_REDUCE_GROUP, (unsigned)p.rblocks, 256, BN}, out, max_out, n);
+    return n;
 }

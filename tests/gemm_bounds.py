@@ -241,7 +241,7 @@ FSEL_NAME = {S_B: "S_B", S_BG: "S_BG", S_GC: "S_GC", S_BDR: "S_BDR", S_BDRO: "S_
 
 
 def feature_select(N, epi):
-    """gemm.hip:1749-1763: the epilogue feature mask of a call and the instantiated superset it runs"""
+    """gemm.hip gemm_feature_index: the epilogue feature mask of a call and the instantiated superset it runs"""
     fm = 0
     if epi.get("bias"): fm |= EF_BIAS
     act, pre = epi.get("act", 0), epi.get("preact")
@@ -268,8 +268,9 @@ def _fill(tiles, slots, w):
 
 
 def route(layout, M, N, K, lda, ldb, epi=None, splits=1, ps=3, h192=1, h192l=1, pp_tn=True, tn_min_m=160):
-    """host copy of lav_gemm_bf16's kernel choice (gemm.hip:1675-1931) at the default switches (lav_gemm_select overrides: ps = 11, h192 = 7,
-    h192l = 9, pp_tn = 2).  Returns a list of launches [(kernel name, (tile rows, tile cols))] in order."""
+    """host copy of lav_gemm_bf16's kernel choice (gemm.hip gemm_plan / gemm_plan_part) at the default switches (lav_gemm_select overrides:
+    ps = 11, h192 = 7, h192l = 9, pp_tn = 2, tn_min_m = 12).  Returns a list of launches [(kernel name, (tile rows, tile cols))] in order.
+    tests/test_gemm_layernorm_bounds_host.py holds it to the library's own plan (lav_gemm_plan) over a sweep of calls."""
     epi = epi or {}
     out = epi.get("out", "bf16")
     kps = ((K + splits - 1) // splits + 63) // 64 * 64
@@ -341,9 +342,9 @@ def route(layout, M, N, K, lda, ldb, epi=None, splits=1, ps=3, h192=1, h192l=1, 
     return r
 
 
-def grouped_route(jobs, splits, tn_min_m=160):
-    """lav_gemm_tn_grouped (gemm.hip:1940-1961): one ping-pong launch when every job fits it, else the jobs one by one"""
-    ok = True
+def grouped_route(jobs, splits, tn_min_m=160, pp_tn=True):
+    """lav_gemm_tn_grouped (gemm.hip tn_group_fits / tn_group_plan): one ping-pong launch when every job fits it, else the jobs one by one"""
+    ok = bool(pp_tn)
     for q in jobs:
         mm = tn_min_m if q["N"] >= 512 else max(tn_min_m, 256)
         ok = ok and q["M"] >= mm and q["N"] % 256 == 0 and q["K"] >= 32 and q["K"] % 32 == 0 and (
@@ -351,7 +352,8 @@ def grouped_route(jobs, splits, tn_min_m=160):
     if not ok:
         r = []
         for q in jobs:
-            r += route(2, q["M"], q["N"], q["K"], q["M"], q["N"], dict(out="acc", k_keep_rpg=q.get("k_keep_rpg")), q.get("fallback_splits", 1))
+            r += route(2, q["M"], q["N"], q["K"], q["M"], q["N"], dict(out="acc", k_keep_rpg=q.get("k_keep_rpg")), q.get("fallback_splits", 1),
+                       pp_tn=pp_tn, tn_min_m=tn_min_m)
         return r
     r = [("gemm_pp_group_kernel", (256, 256))]
     sp = []

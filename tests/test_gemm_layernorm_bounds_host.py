@@ -147,7 +147,7 @@ def test_gemm_mutation_is_rejected(mut):
 
 
 def test_route_table_host_selector():
-    """the host copy of the selector on shapes whose choice is worked out by hand from gemm.hip:1765-1931"""
+    """the host copy of the selector on shapes whose choice is worked out by hand from gemm_plan_part (gemm.hip)"""
     assert GB.route(0, 193, 136, 192, 192, 192) == [("gemm_kernel", (128, 128))]
     assert GB.route(0, 8448, 2048, 128, 128, 128, dict(bias=True, act=1, preact="grad")) == [("gemm_ps_kernel", (192, 256))]
     assert GB.route(0, 8448, 2048, 128, 128, 128, dict(bias=True, act=1, preact="grad"), ps=0) == [("gemm_h192l_kernel", (192, 256))]
@@ -157,6 +157,289 @@ def test_route_table_host_selector():
     assert GB.route(2, 1024, 512, 7840, 1024, 512, dict(out="acc", k_keep_rpg=245), 3) == [("gemm_pp_kernel", (256, 256)), ("tn_reduce_kernel", (256, 128))]
     r = GB.route(2, 768, 768, 30280, 768, 768, dict(out="acc"), 4)
     assert [k for k, _ in r] == ["gemm_pp_kernel", "tn_reduce_kernel", "gemm_kernel"]
+
+
+
+# ---- the library's own route plan (lav_gemm_plan, no device) against the host copy ------------------------------------------------------------
+SEL = {"ps": 11, "h192": 7, "h192l": 9, "pp_tn": 2, "tn_min_m": 12, "group_n": 6, "dbg": 5}
+_PTR = 4096          # a non-null, 16-byte aligned stand-in: the plan only tests the epilogue's pointers for presence
+
+
+def _c_epilogue(epi):
+    """the lav_gemm_epilogue of a gemm_bounds epilogue dict (as tests/test_gpu_gemm_bounds.py and hip.gemm fill it)"""
+    from lavender_amd import _lib
+    e = _lib.GemmEpilogue()
+    e.alpha, e.rows_per_group, e.k_rows_per_group = epi.get("alpha", 1.0), 1, 1
+    e.bias = _PTR if epi.get("bias") else None
+    e.act = epi.get("act", 0)
+    if epi.get("preact"):
+        e.preact, e.preact_is_grad = _PTR, {"value": 0, "grad": 1, "byte": 2}[epi["preact"]]
+    if epi.get("gelu_in"):
+        e.gelu_in, e.gelu_in_is_grad = _PTR, {"value": 0, "grad": 1, "byte": 2}[epi["gelu_in"]]
+    e.dropout_p = 0.1 if epi.get("drop") else 0.0
+    e.row_scale = _PTR if epi.get("rscale") else None
+    e.residual = _PTR if epi.get("res") else None
+    e.colsum = _PTR if epi.get("colsum") else None
+    e.out_mode = {"bf16": 0, "fp32": 1, "acc": 2, "fp16": 3}[epi.get("out", "bf16")]
+    if epi.get("k_keep_rpg"):
+        e.k_keep, e.k_rows_per_group = _PTR, epi["k_keep_rpg"]
+    e.rowsum_a = _PTR if epi.get("rowsum") else None
+    e.a_rowmap = _PTR if epi.get("a_rowmap") else None
+    e.c_pad_writable, e.assign = int(bool(epi.get("c_pad"))), int(bool(epi.get("assign")))
+    return e
+
+
+def _launches(n, out, what):
+    from lavender_amd import _lib
+    assert n > 0, f"{what}: the library refuses the call (rc={n}): {_lib.lib.lav_last_error()}"
+    return [(out[i].kernel.decode(), (out[i].tile_rows, out[i].tile_cols)) for i in range(n)]
+
+
+def _plan(layout, M, N, K, lda, ldb, ldc, epi, splits):
+    import ctypes as C
+    from lavender_amd import _lib
+    out = (_lib.GemmLaunchInfo * 4)()
+    n = _lib.lib.lav_gemm_plan(layout, M, N, K, lda, ldb, ldc, C.byref(_c_epilogue(epi)), splits, out, 4)
+    return _launches(n, out, (layout, M, N, K, lda, ldb, ldc, epi, splits))
+
+
+def _grouped_plan(jobs, splits):
+    from lavender_amd import _lib
+    arr = (_lib.GemmTnJob * len(jobs))()
+    for q, j in zip(arr, jobs):
+        q.M, q.N, q.K, q.lda, q.ldb, q.ldc = j["M"], j["N"], j["K"], (j["M"] + 7) // 8 * 8, (j["N"] + 7) // 8 * 8, (j["N"] + 3) // 4 * 4
+        if j.get("k_keep_rpg"):
+            q.k_keep, q.k_rows_per_group = _PTR, j["k_keep_rpg"]
+        q.alpha, q.fallback_splits = 1.0, j.get("fallback_splits", 1)
+    out = (_lib.GemmLaunchInfo * 16)()
+    return _launches(_lib.lib.lav_gemm_tn_grouped_plan(len(jobs), arr, splits, out, 16), out, (jobs, splits))
+
+
+class _switches:
+    """lav_gemm_select overrides for a block, restored afterwards"""
+
+    def __init__(self, **over):
+        self.over = over
+
+    def __enter__(self):
+        from lavender_amd import _lib
+        self.old = {k: _lib.lib.lav_gemm_select(SEL[k], int(v)) for k, v in self.over.items()}
+
+    def __exit__(self, *exc):
+        from lavender_amd import _lib
+        for k, v in self.old.items():
+            _lib.lib.lav_gemm_select(SEL[k], v)
+
+
+def _route_kw(over):
+    return {k: v for k, v in over.items() if k not in ("group_n", "dbg")}          # the tile walk and the probe bits change no kernel choice
+
+
+def _ld(layout, M, N, K):
+    """contiguous leading dimensions (rows padded to 8 elements), as test_gpu_gemm_bounds._operands builds them"""
+    pad = lambda n: (n + 7) // 8 * 8
+    return (pad(K), pad(K)) if layout == 0 else (pad(K), pad(N)) if layout == 1 else (pad(M), pad(N))
+
+
+def test_plan_matches_route_on_the_gpu_cases():
+    """every case of tests/test_gpu_gemm_bounds.py at the lav_gemm_select settings it runs it with: the library's plan and gemm_bounds.route name
+    the same kernels with the same tiles in the same order"""
+    from tests.test_gpu_gemm_bounds import CASES, GROUPS
+    for cid, (layout, M, N, K, epi, splits, over, want) in CASES.items():
+        out = epi.get("out", "bf16")
+        lda, ldb = _ld(layout, M, N, K)
+        lda += epi.get("lda_pad", 0) if layout != 2 else 0
+        ldc = (N + 7) // 8 * 8 + epi.get("ldc_pad", 0)
+        with _switches(**over):
+            got = _plan(layout, M, N, K, lda, ldb, ldc, dict(epi, out=out), splits)
+        host = GB.route(layout, M, N, K, lda, ldb, dict(epi, out=out), splits, **over)
+        assert got == host, f"{cid}: lav_gemm_plan {got}, gemm_bounds.route {host}"
+        if want is not None:
+            assert [k for k, _ in got][:len(want)] == want or cid.startswith("matrix_") or "_splits" in cid, (cid, got, want)
+    for gid, (spec, splits, want) in GROUPS.items():
+        jobs = [dict(M=M, N=N, K=K, k_keep_rpg=rpg, fallback_splits=2) for (M, N, K, rpg, _) in spec]
+        got, host = _grouped_plan(jobs, splits), GB.grouped_route(jobs, splits)
+        assert got == host, f"{gid}: lav_gemm_tn_grouped_plan {got}, gemm_bounds.grouped_route {host}"
+
+
+# GEMM calls of the bench models (bench.py: cfg2 = Swin-B 224^2, 32 text tokens, batch 32; cfg4 = Swin-L 384^2, batch 8; cfg5 = retrieval, Swin-B,
+# 26 text tokens, 8 x 8 pairs; 5 frames each), from the model dimensions: every nn.Linear (rows, out, in) of the Swin stages (video_swin.SWIN_SIZES:
+# each frame is a clip of its own, rows = B * 5 * (S / 4)^2 / 4^stage, C = E * 2^stage), the patch merging, the 12 + 12 BERT layers (hidden 768,
+# FFN 3072, rows = sequences * (5 * ((S / 32)^2 + 1) + X)) and the MLM head (30522-wide vocabulary), as forward (layout 0), input-gradient
+# (layout 1) and weight-gradient (layout 2) calls with the epilogues and split factors the step uses.
+def _model_linears(size, S, X, B, pairs=None):
+    from lavender_amd.video_swin import SWIN_SIZES as SIZES
+    E, n = SIZES[size]["embed_dim"], B * 5
+    lin, groups = [], []
+    rows = n * (S // 4) ** 2
+    lin.append((rows, E, 96, 0))
+    for st in range(4):
+        C, R = E << st, rows >> (2 * st)
+        blk = [(R, 3 * C, C), (R, C, C), (R, 4 * C, C), (R, C, 4 * C)]
+        lin += [(r, o, i, R // n) for r, o, i in blk]
+        groups.append(([(o, i) for _, o, i in blk], R, R // n))
+        if st < 3:
+            lin.append((R // 4, 2 * C, 4 * C, 0))
+    tok = (S // 32) ** 2
+    lin.append((n * tok, 768, 8 * E, 0))
+    seqs = pairs or n
+    R = seqs * (5 * (tok + 1) + X)
+    blk = [(R, 2304, 768), (R, 768, 768), (R, 3072, 768), (R, 768, 3072)]
+    lin += [(r, o, i, 0) for r, o, i in blk] + [(R, 768, 768, 0), (n * X, 768, 768, 0), (seqs * X, 768, 768, 0), (seqs * X, 30522, 768, 0)]
+    groups.append(([(o, i) for _, o, i in blk], R, 0))
+    return lin, groups
+
+
+FWD_EPI = [dict(), dict(bias=True), dict(bias=True, act=1, preact="grad"), dict(bias=True, act=1, preact="byte"), dict(bias=True, drop=True, rscale=True, res=True),
+           dict(bias=True, drop=True, res="fp16", out="fp16"), dict(bias=True, drop=True, res="ln", out="fp32"), dict(bias=True, c_pad=True),
+           dict(bias=True, res=True, a_rowmap=True)]
+BWD_EPI = [dict(), dict(gelu_in="grad", colsum=True), dict(gelu_in="byte", rscale=True, colsum=True), dict(colsum=True), dict(rscale=True, colsum=True)]
+
+
+def test_plan_matches_route_on_the_bench_models():
+    from lavender_amd import hip
+    n = 0
+    for size, S, X, B, pairs in (("base", 224, 32, 32, None), ("large", 384, 32, 8, None), ("base", 224, 26, 8, 64)):
+        lin, groups = _model_linears(size, S, X, B, pairs)
+        for R, o, i, rpg in lin:
+            calls = [(0, R, o, i, e, 1) for e in FWD_EPI if not e.get("a_rowmap") or (o % 256 == 0 and i % 64 == 0)]
+            calls += [(1, R, i, o, e, 1) for e in BWD_EPI] + [(1, R, i, o, {}, hip.splits_nn(R, i, o) if i % 8 == 0 else 1)]
+            for keep in ((0, rpg) if rpg else (0,)):
+                e = dict(out="acc", rowsum=True, **({"k_keep_rpg": keep} if keep else {}))
+                sp = hip.splits_for(o, i, R, bool(keep))
+                calls += [(2, o, i, R, e, sp), (2, o, i, R, dict(e, assign=o % 4 == 0 and i % 4 == 0), sp), (2, o, i, R, e, 1)]
+            for layout, M, N, K, e, sp in calls:
+                lda, ldb = _ld(layout, M, N, K)
+                ldc = (N + 7) // 8 * 8
+                got, host = _plan(layout, M, N, K, lda, ldb, ldc, e, sp), GB.route(layout, M, N, K, lda, ldb, e, sp)
+                assert got == host, f"{size} {S}: {(layout, M, N, K, e, sp)}: lav_gemm_plan {got}, gemm_bounds.route {host}"
+                n += 1
+        for shapes, K, rpg in groups:
+            for keep in ((0, rpg) if rpg else (0,)):
+                jobs = [dict(M=M, N=N, K=K, k_keep_rpg=keep, fallback_splits=hip.splits_for(M, N, K, bool(keep))) for M, N in shapes]
+                sp = hip.group_splits_for(shapes, K)
+                got, host = _grouped_plan(jobs, max(sp, 1)), GB.grouped_route(jobs, max(sp, 1))
+                assert got == host, f"{size} {S}: grouped {jobs}: lav_gemm_tn_grouped_plan {got}, gemm_bounds.grouped_route {host}"
+                if not keep:
+                    assert (sp > 0) == (got[0][0] == "gemm_pp_group_kernel"), (shapes, K, sp, got)
+                n += 1
+    print(f"{n} model calls")
+    assert n > 1000
+
+
+# ---- seeded random sweep of valid calls ---------------------------------------------------------------------------------------------------------
+SWEEP_EPI = FWD_EPI + BWD_EPI + [
+    dict(bias=True, drop=True, rscale=True, res="ln", out="fp32"), dict(bias=True, drop=True, rscale=True, res="fp16", out="fp16"),
+    dict(act=2, preact="grad", gelu_in="value", drop=True, colsum=True), dict(bias=True, act=1, preact="value"), dict(act=2), dict(out="fp32"),
+    dict(bias=True, out="fp16"), dict(out="acc"), dict(out="acc", bias=True), dict(gelu_in="value"), dict(bias=True, act=1, gelu_in="grad")]
+SWEEP_SWITCHES = [dict(ps=ps, h192=h, h192l=hl, pp_tn=pp, tn_min_m=mm, group_n=gn, dbg=dbg)
+                  for ps, h, hl, pp, mm, gn, dbg in [(3, 1, 1, 1, 160, -1, 0), (0, 1, 1, 1, 160, 0, 0), (1, 1, 0, 1, 256, 4, 1), (2, 1, 1, 0, 160, -1, 2),
+                                                     (0, 1, 0, 0, 300, 2, 4), (3, 0, 1, 1, 128, -1, 0), (0, 0, 0, 1, 160, -1, 0), (1, 1, 1, 0, 256, 0, 0)]]
+
+
+def _pick(rng, xs):
+    return xs[int(rng.integers(len(xs)))]
+
+
+def _random_call(rng):
+    """one valid lav_gemm_bf16 call around the thresholds of the route: (layout, M, N, K, lda, ldb, ldc, epilogue dict, splits)"""
+    layout = int(rng.integers(3))
+    M = max(1, _pick(rng, [160, 256, 2048, 192, 128, 512, 4096, 4289, 8448, 20481, 45120, int(rng.integers(1, 60000))]) + _pick(rng, [-1, 0, 0, 1, 31, -97]))
+    N = max(1, _pick(rng, [256, 512, 768, 1024, 2048, 3072, 256 * int(rng.integers(1, 40)), 128 * int(rng.integers(1, 40))])
+            + _pick(rng, [0, 0, 0, 0, 4, 8, 12, 128, 132, 136, -8, -4, 1, 2, 3, 5, 6, 7, -128, -250]))
+    if rng.random() < 0.15:                                  # outputs that under-fill the last round of 256-row tiles: the 192-row tiles
+        M, N = _pick(rng, [(4289, 2048), (8448, 2048), (45120, 768), (45120, 2304), (20481, 768)])
+    K = max(1, _pick(rng, [64, 128, 768, 1024, 2048, 1984, 2112, 3072, 7840, 30280, 64 * int(rng.integers(1, 600))]) + _pick(rng, [0, 0, 0, 32, -32, 4, 36, -20, 1, 63]))
+    if layout == 2:
+        epi = dict(_pick(rng, [dict(out="acc")] * 8 + [dict(out="fp32"), dict(out="acc", bias=True), dict(), dict(out="acc", colsum=True)]))
+        if rng.random() < 0.5:
+            epi["rowsum"] = True
+        if rng.random() < 0.4:
+            g128 = -(-K // 128)                              # rows per group that give exactly 128 groups: the cap of the ping-pong kernel
+            epi["k_keep_rpg"] = max(1, _pick(rng, [16, 31, 32, 33, 63, 64, 65, 245, 256, g128, g128 - 1, g128 + 1, -(-K // 129), K]))
+    else:
+        epi = dict(_pick(rng, SWEEP_EPI))
+        if epi.get("a_rowmap") and not (layout == 0 and N % 256 == 0 and K % 64 == 0):
+            del epi["a_rowmap"]
+        if rng.random() < 0.15:
+            epi["c_pad"] = True
+    out = epi.get("out", "bf16")
+    splits = int(rng.integers(1, 17)) if rng.random() < 0.6 else 1
+    if not (out == "acc" or (out == "bf16" and layout != 2 and not (set(epi) - {"c_pad"}) and N % 8 == 0)):
+        splits = 1                                           # split-K: fp32 accumulate, or a bf16 output without epilogue and N % 8 == 0
+    if epi.get("a_rowmap"):
+        splits = 1
+    if layout == 2 and out == "acc" and rng.random() < 0.4 and (N % 4 == 0 or splits == 1):
+        epi["assign"] = True                                 # with split-K the reduction pass assigns: N % 4 == 0
+    lda, ldb = _ld(layout, M, N, K)
+    if rng.random() < 0.3:                                   # operands on both sides of 2 GiB (the phase-shifted kernels address 32 bits)
+        rows_a, rows_b = (M, N) if layout == 0 else (M, K) if layout == 1 else (K, K)
+        lda = max(lda, ((1 << 30) // rows_a + _pick(rng, [-16, 8, 64])) // 8 * 8)
+        if rng.random() < 0.5:
+            ldb = max(ldb, ((1 << 30) // rows_b + _pick(rng, [-16, 8, 64])) // 8 * 8)
+    ldc = (N + 7) // 8 * 8 + _pick(rng, [0, 0, 8, 16]) if out in ("bf16", "fp16") else (N + 3) // 4 * 4 + _pick(rng, [0, 0, 4, 8])
+    return layout, M, N, K, lda, ldb, ldc, epi, splits
+
+
+def test_plan_matches_route_on_a_random_sweep():
+    """24 000 valid calls (seeded) over the three layouts, every feature set, output mode, split factor, drop-path grouping, the M / N / K
+    thresholds and residues of the route and each lav_gemm_select setting: kernel names, tiles and launch order agree on every one, and the
+    sweep reaches every kernel and every multi-launch form"""
+    import numpy as np
+    rng = np.random.default_rng(20260)
+    seen, fsets, n = set(), set(), 0
+    for over in SWEEP_SWITCHES:
+        calls = [_random_call(rng) for _ in range(3000)]
+        with _switches(**over):
+            got = [_plan(*c) for c in calls]
+        for c, g in zip(calls, got):
+            layout, M, N, K, lda, ldb, ldc, epi, splits = c
+            host = GB.route(layout, M, N, K, lda, ldb, epi, splits, **_route_kw(over))
+            assert g == host, f"{c} at {over}: lav_gemm_plan {g}, gemm_bounds.route {host}"
+            seen.add(tuple(k for k, _ in g))
+            seen.update(g)
+            fsets.add((g[0][0], GB.FSEL_NAME[GB.feature_select(N, epi)]) if layout != 2 else None)
+            n += 1
+    assert n >= 20000
+    for k in (("gemm_kernel", (128, 128)), ("gemm_big_kernel", (256, 128)), ("gemm_huge_kernel", (256, 256)), ("gemm_h192_kernel", (192, 256)),
+              ("gemm_h192l_kernel", (192, 256)), ("gemm_ps_kernel", (256, 256)), ("gemm_ps_kernel", (192, 256)), ("gemm_pp_kernel", (256, 256)),
+              ("tn_reduce_kernel", (256, 128)), ("tn_reduce_kernel", (128, 128)), ("splitk_reduce_bf16_kernel", (256, 256)),
+              ("splitk_reduce_bf16_kernel", (128, 128)), ("gemm_pp_kernel", "tn_reduce_kernel", "gemm_kernel"), ("gemm_huge_kernel", "tn_reduce_kernel", "gemm_kernel"),
+              ("gemm_big_kernel", "gemm_kernel")):
+        assert k in seen, f"the sweep never reaches {k}"
+    for kern, sets in (("gemm_big_kernel", 6), ("gemm_huge_kernel", 6), ("gemm_ps_kernel", 5), ("gemm_h192_kernel", 5), ("gemm_h192l_kernel", 5)):
+        assert len({f for f in fsets if f and f[0] == kern}) == sets, (kern, sorted(f for f in fsets if f and f[0] == kern))
+
+
+def test_grouped_plan_matches_route_and_hip_split_heuristic():
+    """random groups of 1 ... 4 weight-gradient jobs with a common contraction: lav_gemm_tn_grouped_plan against gemm_bounds.grouped_route at each
+    pp_tn / tn_min_m setting, and hip.group_splits_for(shapes, K) > 0 exactly when the library takes the grouped launch (jobs without k_keep,
+    which hip.py does not see; hip.py reads LAV_GEMM_TN_MINM itself: its value must be the library's)"""
+    import numpy as np
+    from lavender_amd import _lib, hip
+    mm = _lib.lib.lav_gemm_select(SEL["tn_min_m"], 160)
+    _lib.lib.lav_gemm_select(SEL["tn_min_m"], mm)
+    assert mm == hip._TN_MINM, (mm, hip._TN_MINM)
+    rng = np.random.default_rng(7)
+    grouped = 0
+    for over in (dict(), dict(pp_tn=0), dict(tn_min_m=256), dict(tn_min_m=300, pp_tn=1)):
+        for _ in range(1000):
+            K = max(32, _pick(rng, [512, 2048, 7840, 30280, 45120, 32 * int(rng.integers(1, 300))]) + _pick(rng, [0, 0, 0, 0, 32, 16, -1]))
+            rpg = _pick(rng, [0, 0, 0, 245, 256, 64, 63, 32, -(-K // 128), -(-K // 129)])
+            jobs = [dict(M=max(1, _pick(rng, [160, 256, 192, 384, 768, 1024, 3072]) + _pick(rng, [0, 0, 0, -1, 1])),
+                         N=_pick(rng, [256, 512, 768, 1024, 3072, 384, 260]), K=K, k_keep_rpg=rpg, fallback_splits=int(rng.integers(1, 12)))
+                    for _ in range(int(rng.integers(1, 5)))]
+            splits = int(rng.integers(1, 9))
+            with _switches(**over):
+                got = _grouped_plan(jobs, splits)
+            host = GB.grouped_route(jobs, splits, **over)
+            assert got == host, f"{jobs} splits {splits} at {over}: lav_gemm_tn_grouped_plan {got}, gemm_bounds.grouped_route {host}"
+            is_group = got[0][0] == "gemm_pp_group_kernel"
+            assert not is_group or len(got) <= 2
+            grouped += is_group
+            if not over and not rpg:
+                assert (hip.group_splits_for([(j["M"], j["N"]) for j in jobs], K) > 0) == is_group, (jobs, got)
+    assert grouped > 200
 
 
 # ---- LayerNorm --------------------------------------------------------------------------------------------------------------------------

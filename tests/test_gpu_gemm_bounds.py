@@ -51,8 +51,8 @@ CASES = {
     "tn_generic_epilogue": (2, 200, 256, 512, dict(out="fp32"), 1, {}, ["gemm_kernel"]),
 }
 
-# every large-tile kernel of layouts 0 / 1 with every epilogue feature set it is instantiated for (LAV_LAUNCH_BY_FEATURES, LAV_PS_256, LAV_PS6,
-# LAV_H192 in gemm.hip).  Dropout cases store through a padded ldc (the mask index is row * N + col, not row * ldc + col); M tails of 191 and 255
+# every large-tile kernel of layouts 0 / 1 with every epilogue feature set it is instantiated for (the gemm_kernels table
+# in gemm.hip).  Dropout cases store through a padded ldc (the mask index is row * N + col, not row * ldc + col); M tails of 191 and 255
 # rows past a 256-row multiple; A read through a strided view on the 256 x 128 and 192-row kernels.
 FSETS = {
     "S_B": dict(bias=True),
