@@ -385,6 +385,24 @@ int lav_cross_entropy_f32_fwd_bwd(void* stream, int rows, int V, float* logits, 
                                   float* loss_sum, float grad_scale, int write_grad);
 
 /* ---------------------------------------------------------------------------------------------
+ * Captioning loss (model_for_captioning.py:10-37 on the labelled rows, main_caption.py:225-230): label smoothing as the KL
+ * divergence to q (q_t = 1 - label_smoothing, q_c = label_smoothing / (V - 1) elsewhere), "drop the worst" rows, the arg-max
+ * accuracy read-out and the in-place logit gradient.  logits: bf16 (rows, ld), V valid columns, ld % 8 == 0; labels int64 in
+ * [0, V), -1 = ignore (a label outside [0, V) is treated as -1, never read as a column).  Per labelled row r, in fp32:
+ *   row_loss[r] = sum_c q_c (log q_c - log p_c), row_lse[r] = log sum exp, correct[r] = (arg-max column, lowest index on a tie, == label);
+ * unlabelled rows write 0.  k = number of rows whose loss is averaged, computed by the caller from the labelled-row count it knows:
+ * that count when select == 0 (every labelled row is kept: one launch over the logits, the passes of lav_cross_entropy_fwd_bwd), and
+ * int(count * (1 - drop_worst_ratio)) when select != 0: kept[r] = 1 for the k labelled rows that come first by (loss ascending, row
+ * ascending; NaN last), found by counting -- no sort, no atomics -- and the gradient is written by a second launch behind the row losses.
+ * out[0] = sum of the kept losses, out[1] = k, out[2] = sum of correct, out[3] = number of labelled rows, added in a fixed order
+ * (identical bits run to run); the loss is out[0] / out[1].  write_grad != 0 overwrites the logits IN PLACE with (p - q) / k on kept
+ * rows and 0 on dropped rows, unlabelled rows and the padding columns [V, ld); write_grad == 0 leaves them untouched.
+ * row_loss, row_lse (fp32) and correct, kept (int32) hold `rows` elements each, out four floats; nothing needs zeroing. */
+int lav_caption_loss_fwd_bwd(void* stream, int rows, int V, void* logits, long ld, const int64_t* labels, float label_smoothing,
+                             int k, int select, float* row_loss, float* row_lse, int32_t* correct, int32_t* kept, float* out,
+                             int write_grad);
+
+/* ---------------------------------------------------------------------------------------------
  * Video-text matching score head of the task-specific pre-training variant: the last layer of
  * self.fc = Sequential(Dropout, Linear(H,2H), ReLU, Linear(2H,1)) (main_pretrain_task_specific.py:128-133)
  * and "out_vtm = fc(out[:, Lv]).view(B, O) / temp" (:168-170).  Dropout and Linear+ReLU run through

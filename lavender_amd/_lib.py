@@ -191,6 +191,7 @@ _SIGS = {
     "lav_scale_by_count": (i32, [vp, i64, vp, vp, f32]),
     "lav_scale_by_scalar": (i32, [vp, i64, vp, i32, vp]),
     "lav_cross_entropy_f32_fwd_bwd": (i32, [vp, i32, i32, vp, i64, vp, vp, f32, i32]),
+    "lav_caption_loss_fwd_bwd": (i32, [vp, i32, i32, vp, i64, vp, f32, i32, i32, vp, vp, vp, vp, vp, i32]),
     "lav_transpose_bf16_batched": (i32, [vp, i32, vp, i32, vp, vp]),
     "lav_pair_score_fwd": (i32, [vp, i32, i32, vp, i64, vp, vp, f32, i32, vp, i64]),
     "lav_pair_score_bwd": (i32, [vp, i32, i32, vp, i64, i32, f32, vp, i64, vp, i64, vp, vp, i64, vp, vp]),

@@ -31,7 +31,9 @@ _DEFAULTS = dict(
     lr=1.2e-5, decay=1e-3, size_epoch=20, seed=88, logging_steps=20, vis_backbone_lr_mul=1.0, max_grad_norm=-1.0,
     deepspeed=False, use_checkpoint=False, temp=1.0, local_rank=0, size_part=8, pretrain_tasks=["mtm", "vtm"],
     p_mask=0.15, enable_task_token=False, task_token=None, enable_prompt=False, mask_pos='append', path_ckpt='',
-    multi_clip_testing=False, tokenizer='bert-base-uncased')
+    multi_clip_testing=False, tokenizer='bert-base-uncased',
+    # captioning (main_caption.py, model_for_captioning.py:10-37)
+    label_smoothing=0.0, drop_worst_ratio=0.0, drop_worst_after=0, max_gen_length=20)
 
 
 def parse_with_config(argv=None):

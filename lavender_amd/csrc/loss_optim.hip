@@ -1,5 +1,6 @@
 // Cross-entropy (fused forward + in-place logit gradient) and the flat-arena optimizer kernels.  All HBM-bound.
 #include "common.h"
+#include <math.h>
 #include <stdlib.h>
 #include "../../include/lavender_hip.h"
 
@@ -107,6 +108,193 @@ extern "C" int lav_cross_entropy_f32_fwd_bwd(void* stream, int rows, int V, floa
     hipLaunchKernelGGL(ce_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, rows, V, logits, ld, labels, loss_sum,
                        grad_scale, write_grad);
     return lav_check_launch("lav_cross_entropy_f32_fwd_bwd");
+}
+
+// ---- captioning loss (model_for_captioning.py:10-37 on the labelled rows, main_caption.py:225-230) ------------------------------------
+// label smoothing as the KL divergence to q (q_t = 1 - eps, q_c = eps / (V - 1)), "drop the worst" rows, the arg-max accuracy read-out and the
+// in-place logit gradient.  One 256-thread block per row, the passes of ce_kernel: one read for (max, sum-exp, sum of logits, arg-max), one
+// read + write for the gradient.  With the selection on, the gradient pass is a launch of its own behind the row losses (cap_select_kernel).
+// No atomics anywhere: the four totals come from one block that adds the per-row results in a fixed order (bit-identical run to run).
+struct CapArgs {
+    int rows, V, k;
+    bf16_t* logits; long ld; const int64_t* labels;
+    float eps, C, q_other, scale;                          // C(eps, V); eps / (V - 1); 1 / k
+    float* row_loss; float* row_lse; int32_t* correct; int32_t* kept; float* out;
+};
+
+__device__ __forceinline__ void cap_zero_row(bf16_t* x, int nchunk, int tid) {
+    for (int c = tid; c < nchunk; c += 256) *(uint4*)(x + c * 8) = make_uint4(0, 0, 0, 0);
+}
+
+// x <- (softmax(x) - q) * scale on the V valid columns, 0 on the padding columns
+__device__ __forceinline__ void cap_grad_row(bf16_t* x, int nchunk, int V, long label, float lse, float q_target, float q_other, float scale, int tid) {
+    for (int c = tid; c < nchunk; c += 256) {
+        float v[8];
+        uint4 u = *(const uint4*)(x + c * 8);
+        unpack8(u, v);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int col = c * 8 + k;
+            const float g = col < V ? __expf(v[k] - lse) - (col == label ? q_target : q_other) : 0.f;
+            v[k] = g * scale;
+        }
+        *(uint4*)(x + c * 8) = pack8(v);
+    }
+}
+
+// FUSED: no selection, every labelled row is kept -- row results and (write_grad) the gradient in one launch
+template <bool FUSED>
+__global__ __launch_bounds__(256) void cap_row_kernel(CapArgs a, int write_grad) {
+    __shared__ float sm[4], ss[4], sx[4], sb[4];
+    __shared__ int si[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bf16_t* x = a.logits + (long)row * a.ld;
+    const long label = a.labels[row];
+    const int nchunk = (int)(a.ld / 8), V = a.V;
+    if (label < 0 || label >= V) {                         // unlabelled (a label outside [0, V) is never used as a column)
+        if (tid == 0) { a.row_loss[row] = 0.f; a.row_lse[row] = 0.f; a.correct[row] = 0; a.kept[row] = 0; }
+        if (FUSED && write_grad) cap_zero_row(x, nchunk, tid);
+        return;
+    }
+    float m = -INFINITY, s = 0.f, sum = 0.f, best = -INFINITY;
+    int bidx = 0x7fffffff;
+    for (int c = tid; c < nchunk; c += 256) {
+        float v[8];
+        uint4 u = *(const uint4*)(x + c * 8);
+        unpack8(u, v);
+        float cm = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int col = c * 8 + k;
+            if (col >= V) v[k] = -INFINITY; else sum += v[k];
+            cm = fmaxf(cm, v[k]);
+            if (v[k] > best) { best = v[k]; bidx = col; }  // columns ascend within a thread: strict > keeps the lowest index
+        }
+        if (cm > m) { s *= __expf(m - cm); m = cm; }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += __expf(v[k] - m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64), b2 = __shfl_xor(best, o, 64);
+        const int i2 = __shfl_xor(bidx, o, 64);
+        const float mn = fmaxf(m, m2);
+        s = (m == -INFINITY ? 0.f : s * __expf(m - mn)) + (m2 == -INFINITY ? 0.f : s2 * __expf(m2 - mn));
+        m = mn;
+        sum += __shfl_xor(sum, o, 64);
+        if (b2 > best || (b2 == best && i2 < bidx)) { best = b2; bidx = i2; }
+    }
+    if (lane == 0) { sm[wave] = m; ss[wave] = s; sx[wave] = sum; sb[wave] = best; si[wave] = bidx; }
+    __syncthreads();
+    const float M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    float S = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) S += ss[w] * __expf(sm[w] - M);
+    const float lse = M + __logf(S);
+    if (tid == 0) {
+        const float xt = bf2f(x[label]);
+        float B = sb[0];
+        int I = si[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (sb[w] > B || (sb[w] == B && si[w] < I)) { B = sb[w]; I = si[w]; }
+        // sum_c q_c (log q_c - log p_c) = C + lse - (1 - eps) x_t - eps / (V - 1) sum_{c != t} x_c     (the q_c sum to 1)
+        const float SX = (sx[0] + sx[1]) + (sx[2] + sx[3]);
+        a.row_loss[row] = a.eps > 0.f ? (a.C + lse) - (1.f - a.eps) * xt - a.q_other * (SX - xt) : lse - xt;
+        a.row_lse[row] = lse;
+        a.correct[row] = I == (int)label ? 1 : 0;
+        if (FUSED) a.kept[row] = 1;
+    }
+    if (!FUSED || !write_grad) return;
+    __syncthreads();                                       // x[label] read before anybody overwrites it
+    cap_grad_row(x, nchunk, V, label, lse, 1.f - a.eps, a.q_other, a.scale, tid);
+}
+
+// selection in the style of rank_kernel (retrieval.hip): a labelled row is kept when fewer than k labelled rows sort before it by
+// (loss ascending, row ascending) -- torch.topk(largest=False) up to its order among equal losses; NaN sorts last.  Then the gradient pass.
+__global__ __launch_bounds__(256) void cap_select_kernel(CapArgs a, int write_grad) {
+    __shared__ int wred[4];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    bf16_t* x = a.logits + (long)row * a.ld;
+    const long label = a.labels[row];
+    const int nchunk = (int)(a.ld / 8);
+    if (label < 0 || label >= a.V) {
+        if (write_grad) cap_zero_row(x, nchunk, tid);
+        return;
+    }
+    const float mine = a.row_loss[row];
+    const bool mnan = isnan(mine);
+    int cnt = 0;
+    for (int r = tid; r < a.rows; r += 256) {
+        const long lr = a.labels[r];
+        if (lr < 0 || lr >= a.V) continue;
+        const float l = a.row_loss[r];
+        const bool lnan = isnan(l);
+        const bool before = mnan ? (!lnan || r < row) : (!lnan && (l < mine || (l == mine && r < row)));
+        cnt += before ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((tid & 63) == 0) wred[tid >> 6] = cnt;
+    __syncthreads();
+    const bool keep = (wred[0] + wred[1]) + (wred[2] + wred[3]) < a.k;
+    if (tid == 0) a.kept[row] = keep ? 1 : 0;
+    if (!write_grad) return;
+    if (keep) cap_grad_row(x, nchunk, a.V, label, a.row_lse[row], 1.f - a.eps, a.q_other, a.scale, tid);
+    else cap_zero_row(x, nchunk, tid);
+}
+
+// out = {sum of the kept row losses, k, number of correct rows, number of labelled rows}: one block, fixed order
+__global__ __launch_bounds__(256) void cap_total_kernel(CapArgs a) {
+    __shared__ float sl[4];
+    __shared__ int sc[4], sn[4];
+    const int tid = threadIdx.x;
+    float ls = 0.f;
+    int nc = 0, nl = 0;
+    for (int r = tid; r < a.rows; r += 256) {
+        const long lr = a.labels[r];
+        if (lr < 0 || lr >= a.V) continue;
+        ++nl;
+        nc += a.correct[r];
+        if (a.kept[r]) ls += a.row_loss[r];
+    }
+    ls = wave_sum(ls);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { nc += __shfl_xor(nc, o, 64); nl += __shfl_xor(nl, o, 64); }
+    if ((tid & 63) == 0) { sl[tid >> 6] = ls; sc[tid >> 6] = nc; sn[tid >> 6] = nl; }
+    __syncthreads();
+    if (tid == 0) {
+        a.out[0] = (sl[0] + sl[1]) + (sl[2] + sl[3]);
+        a.out[1] = (float)a.k;
+        a.out[2] = (float)((sc[0] + sc[1]) + (sc[2] + sc[3]));
+        a.out[3] = (float)((sn[0] + sn[1]) + (sn[2] + sn[3]));
+    }
+}
+
+extern "C" int lav_caption_loss_fwd_bwd(void* stream, int rows, int V, void* logits, long ld, const int64_t* labels, float label_smoothing,
+                                        int k, int select, float* row_loss, float* row_lse, int32_t* correct, int32_t* kept, float* out,
+                                        int write_grad) {
+    LAV_REQUIRE(rows > 0 && V > 1 && logits && labels && row_loss && row_lse && correct && kept && out, "lav_caption_loss_fwd_bwd: bad arguments");
+    LAV_REQUIRE(ld % 8 == 0 && ld >= V, "lav_caption_loss_fwd_bwd: ld must be a multiple of 8 and >= V");
+    LAV_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "lav_caption_loss_fwd_bwd: label_smoothing %g outside [0, 1)", (double)label_smoothing);
+    LAV_REQUIRE(k >= 0 && k <= rows, "lav_caption_loss_fwd_bwd: k = %d kept rows of %d", k, rows);
+    CapArgs a;
+    a.rows = rows; a.V = V; a.k = k; a.logits = (bf16_t*)logits; a.ld = ld; a.labels = labels;
+    const double e = (double)label_smoothing;
+    a.eps = label_smoothing;
+    a.C = (float)((1.0 - e) * log(1.0 - e) + (e > 0.0 ? e * log(e / (double)(V - 1)) : 0.0));
+    a.q_other = (float)(e / (double)(V - 1));
+    a.scale = k > 0 ? 1.f / (float)k : 0.f;
+    a.row_loss = row_loss; a.row_lse = row_lse; a.correct = correct; a.kept = kept; a.out = out;
+    hipStream_t st = (hipStream_t)stream;
+    if (select) {
+        hipLaunchKernelGGL(cap_row_kernel<false>, dim3(rows), dim3(256), 0, st, a, 0);
+        hipLaunchKernelGGL(cap_select_kernel, dim3(rows), dim3(256), 0, st, a, write_grad);
+    } else {
+        hipLaunchKernelGGL(cap_row_kernel<true>, dim3(rows), dim3(256), 0, st, a, write_grad);
+    }
+    hipLaunchKernelGGL(cap_total_kernel, dim3(1), dim3(256), 0, st, a);
+    return lav_check_launch("lav_caption_loss_fwd_bwd");
 }
 
 __global__ __launch_bounds__(256) void scale_bf16_kernel(long n8, bf16_t* x, const float* cnt, float gscale) {

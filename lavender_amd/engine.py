@@ -1269,3 +1269,34 @@ class CrossEntropyFn(torch.autograd.Function):
 
 # Set to True only by a caller that guarantees an upstream gradient of exactly 1 (skips the scale launch above).
 CrossEntropyFn.assume_unit_grad = False
+
+
+class CaptionLossFn(torch.autograd.Function):
+    """CaptioningLoss (model_for_captioning.py:10-37) on the labelled rows of a (rows, V) logits view: (loss, stats) with stats (4,) fp32 =
+    [sum of the kept row losses, k, number of rows whose arg-max is the label, number of labelled rows] (lav_caption_loss_fwd_bwd).  `k` rows
+    are averaged (the caller derives it from the labelled-row count it knows), `select` turns the drop-the-worst selection on.  As with
+    CrossEntropyFn, training consumes the logits buffer: it is overwritten in place with d(loss)/d(logits), unless `keep_logits`."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, label_smoothing, k, select, keep_logits=False):
+        assert logits.dim() == 2 and logits.dtype == torch.bfloat16 and logits.stride(-1) == 1 and logits.stride(0) % 8 == 0, \
+            "logits must be a (rows, V) view of a row-padded bf16 buffer (as produced by the MLM head)"
+        train = ctx.needs_input_grad[0]
+        if keep_logits and train:
+            src = logits
+            logits = torch.empty((src.shape[0], src.stride(0)), dtype=src.dtype, device=src.device)[:, :src.shape[1]]
+            logits.copy_(src)
+        stats, row_loss, correct, kept = K.caption_loss(logits, logits.shape[-1], labels.contiguous(), label_smoothing, k, select, train)
+        ctx.grad_buf = logits if train else None
+        ctx.mark_non_differentiable(stats)
+        ctx.rows = (row_loss, correct, kept)               # per-row results, for tests and diagnostics
+        return stats[0] / stats[1], stats
+
+    @staticmethod
+    def backward(ctx, g, _):
+        buf = ctx.grad_buf
+        if buf is None:
+            return None, None, None, None, None, None
+        # the upstream gradient is applied on the device, as in CrossEntropyFn.backward
+        K.scale_by_scalar(buf, buf.shape[0] * buf.stride(0), g.reshape(1).float())
+        return buf, None, None, None, None, None

@@ -612,6 +612,18 @@ def cross_entropy(logits2d, V, labels, loss_sum, grad_scale, write_grad):
                                             float(grad_scale), int(write_grad)), "lav_cross_entropy_fwd_bwd")
 
 
+def caption_loss(logits2d, V, labels, label_smoothing, k, select, write_grad):
+    """lav_caption_loss_fwd_bwd on a (rows, V) view of a row-padded bf16 logits buffer: (out (4,) fp32 = [sum of kept losses, k, sum of correct,
+    number of labelled rows], row_loss (rows,) fp32, correct (rows,) int32, kept (rows,) int32); write_grad overwrites the logits with (p - q) / k"""
+    rows, dev = logits2d.shape[0], logits2d.device
+    f = torch.empty((2, rows), dtype=torch.float32, device=dev)          # row losses, row log-sum-exps
+    i = torch.empty((2, rows), dtype=torch.int32, device=dev)            # correct, kept
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    L.check(L.lib.lav_caption_loss_fwd_bwd(_s(), rows, V, _p(logits2d), _ld(logits2d), _p(labels), float(label_smoothing), int(k), int(select),
+                                           _p(f[0]), _p(f[1]), _p(i[0]), _p(i[1]), _p(out), int(write_grad)), "lav_caption_loss_fwd_bwd")
+    return out, f[0], i[0], i[1]
+
+
 def scale_by_count(x, n_elems, loss_sum, gscale):
     L.check(L.lib.lav_scale_by_count(_s(), int(n_elems), _p(x), _p(loss_sum), float(gscale)), "lav_scale_by_count")
 
