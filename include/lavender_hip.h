@@ -763,6 +763,30 @@ int lav_mlm_pair_readout(void* stream, const lav_mlm_pair_readout_desc* d);
  * number and NaNs keep their column order.  A gt outside [0, n_video) gives 0.  One workgroup per row. */
 int lav_retrieval_rank(void* stream, int n_text, int n_video, const float* S, long ldS, const int32_t* gt, int32_t* out);
 
+/* lav_answer_readout: the video-QA read-out of n logit rows of width V (logits (n, ld), ld >= V; dtype 0 = bf16, 1 = fp32), one pass per row
+ * (csrc/qa.hip).  Order of the columns of a row: value descending, a NaN above every number (the order of torch.topk / torch.argmax), the LOWER
+ * index first among equal values (-0 = +0) and among NaNs.
+ *   pred[r]    the first column in that order (arg-max, lowest index on a tie)
+ *   rank[r]    number of columns before column labels[r] in that order: #{c : x_c > x_t, or x_c == x_t and c < t}; -1 where labels[r] == -1.
+ *              A top-k hit is 0 <= rank < k (main_qaoe_mlm_lsmdc_fib.py:115-126; torch.topk leaves the order of ties open, this rule fixes it)
+ *   choice[r]  arg-max over c < n_cand of x[cand[c]] / sum_c x[cand[c]] (main_qamc_mlm.py:159-166: RAW logits, so a negative sum reverses the
+ *              order); the sum and the quotients are fp32, the sum runs in candidate order, the first index wins a tie, a NaN quotient is
+ *              above every number; -1 when n_cand == 0
+ * labels (n) int32 on the device; labels_host: the same values in host memory or NULL -- when given, a label outside [0, V) other than -1 is
+ * rejected (without it the caller vouches for them; the kernel reads no column outside the row either way and treats such a label as -1).
+ * cand_host: n_cand <= LAV_ANSWER_MAX_CAND token ids in HOST memory (they travel as a kernel argument), each in [0, V).  pred / rank / choice:
+ * caller-owned (n) int32 on the device.
+ * splits (1 .. LAV_ANSWER_MAX_SPLITS): each row is cut into that many column ranges, one workgroup each; for splits > 1 a second launch merges
+ * the partials held in `workspace` (device, 8-byte aligned, >= lav_answer_readout_workspace_bytes(n, splits) bytes, else LAV_E_WORKSPACE).
+ * Counts are integers and the best column an integer max, so every split count gives identical outputs.  No atomics, no allocation, no
+ * synchronisation.  A rejected call launches nothing. */
+#define LAV_ANSWER_MAX_CAND 32
+#define LAV_ANSWER_MAX_SPLITS 16
+size_t lav_answer_readout_workspace_bytes(int n, int splits);
+int lav_answer_readout(void* stream, int n, int V, const void* logits, long ld, int dtype, const int32_t* labels, const int32_t* labels_host,
+                       const int32_t* cand_host, int n_cand, int splits, void* workspace, size_t workspace_bytes, int32_t* pred, int32_t* rank,
+                       int32_t* choice);
+
 /* ---------------------------------------------------------------------------------------------
  * Process-wide probe switches: environment variables read ONCE by the library on first use (not part of the contract; every setting
  * computes the same results up to fp32 summation order unless stated).  They exist so that tools/ and profiles/ can A/B a kernel

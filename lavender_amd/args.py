@@ -33,14 +33,16 @@ _DEFAULTS = dict(
     p_mask=0.15, enable_task_token=False, task_token=None, enable_prompt=False, mask_pos='append', path_ckpt='',
     multi_clip_testing=False, tokenizer='bert-base-uncased',
     # captioning (main_caption.py, model_for_captioning.py:10-37)
-    label_smoothing=0.0, drop_worst_ratio=0.0, drop_worst_after=0, max_gen_length=20)
+    label_smoothing=0.0, drop_worst_ratio=0.0, drop_worst_after=0, max_gen_length=20,
+    # video QA (main_qaoe_mlm.py, main_qamc_mlm.py): head, last layer and read-out on the labelled [MASK] rows only (qa_mlm.py)
+    qa_rows=False, size_option=5)
 
 
-def parse_with_config(argv=None):
+def parse_with_config(argv=None, defaults=None):
     """utils/args.py:16-34: every default is overridable by --flag; --config JSON fills what the CLI left unset
-    and may add undeclared keys (type, task, ...)."""
+    and may add undeclared keys (type, task, ...).  defaults: an entry point's own defaults over _DEFAULTS."""
     p = argparse.ArgumentParser(description="lavender_amd pretrain")
-    for k, v in _DEFAULTS.items():
+    for k, v in {**_DEFAULTS, **(defaults or {})}.items():
         if isinstance(v, bool):
             p.add_argument(f"--{k}", type=str_to_bool, nargs='?', const=True, default=v)
         elif isinstance(v, list):
@@ -63,10 +65,10 @@ def parse_with_config(argv=None):
     return args
 
 
-def get_args(argv=None, distributed=True):
+def get_args(argv=None, distributed=True, defaults=None):
     """utils/args.py:245-258: parse, init the process group from the launcher env, derive effective batch."""
     from .dist import dist_init
-    args = parse_with_config(argv)
+    args = parse_with_config(argv, defaults)
     args.setdefault("type", "pretrain")
     args.setdefault("task", "pretrain")
     dist_init(args, distributed)

@@ -622,3 +622,104 @@ class Dataset_RetrievalMlmEval(Dataset_Base):
         img = self._decoder.decode(plans, S).view(len(inputs), nc, T, 3, S, S)
         return {"img": img, "txt": torch.stack([t for _, t, _, _, _ in inputs]), "mask": torch.stack([m for _, _, m, _, _ in inputs]),
                 "tid": [t for _, _, _, t, _ in inputs], "vid": [v for _, _, _, _, v in inputs]}
+
+
+# ---- synthetic video QA (main_qaoe_mlm.py / main_qamc_mlm.py without their TSV files) -------------------------------------------------------
+# bert-base-uncased ids of the word pieces the reference's QA texts are built from
+QA_TOK = {"answer": 3437, ":": 1024, "option": 5724, "0": 1014}        # the digits "0" .. "9" are 1014 .. 1023
+
+
+class SyntheticQA(torch.utils.data.Dataset):
+    """Random clips with question texts laid out as the reference's MLM-head QA datasets lay them out (token ids, no tokenizer model needed):
+
+      kind "oe"  Dataset_QAOE_MLM.str2txt (main_qaoe_mlm.py:18-39): [CLS] q_1 .. q_k  answer : [MASK]  [SEP] [PAD] * (size_txt - k), k <= size_txt - 1,
+                 X = size_txt + 5; items (img, txt, mask, mask_ans), mask_ans = the answer token at the [MASK], -1 elsewhere
+      kind "mc"  Dataset_QAMC_MLM (main_qamc_mlm.py:46-87, mask_pos "append"): the question followed by "option i : words" for each of the
+                 size_option options as ONE text, cut to size_txt - 1 tokens, [CLS] tokens [MASK] [SEP] [PAD] * (size_txt - k), X = size_txt + 3;
+                 items (img, txt, mask, mask_ans, ans_idx), mask_ans = the token of the digit ans_idx at the [MASK]
+
+    Stands in for the TSV datasets of the two entry points; `vocab` bounds the random word ids."""
+
+    def __init__(self, args, n, split, tokzr, kind="oe", vocab=30522):
+        assert kind in ("oe", "mc")
+        self.args, self.n, self.split, self.tokzr, self.kind = args, int(n), split, tokzr, kind
+        self.size_option = int(getattr(args, "size_option", 5))
+        assert 1 <= self.size_option <= 10, "option indices are single digit tokens"
+        self.cls_id, self.sep_id, self.pad_id, self.mask_id = tokzr.convert_tokens_to_ids(
+            [tokzr.cls_token, tokzr.sep_token, tokzr.pad_token, tokzr.mask_token])
+        self.hi = min(30000, int(vocab))
+        assert self.hi > max(QA_TOK.values()) + 10, "vocabulary too small for the QA word pieces"
+        self.ans_tok_ids = [QA_TOK["0"] + i for i in range(self.size_option)]       # Dataset_QAMC_MLM.ans_tok_ids
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def prompt_text(self):
+        return PROMPT_TEXTS["qaoe"] if self.kind == "oe" else PROMPT_TEXTS["qamc"](self.size_option)
+
+    def get_prompt(self):
+        g = torch.Generator().manual_seed(7 if self.kind == "oe" else 9)
+        ids = torch.cat([torch.tensor([self.cls_id]), torch.randint(1000, self.hi, (6,), generator=g), torch.tensor([self.sep_id])])
+        return ids, torch.ones_like(ids)                   # stands in for the tokenized prompt_text: [CLS] words [SEP], mask of ones
+
+    def _words(self, g, k):
+        return torch.randint(1000, self.hi, (k,), generator=g).tolist()
+
+    def text(self, i):
+        """(txt, mask, mask_ans, ans_idx or None) of item i"""
+        g = torch.Generator().manual_seed(i + {"train": 0, "val": 1 << 20, "test": 1 << 21}.get(self.split, 1 << 22))
+        S = int(self.args.size_txt)
+        ans_idx = None
+        if self.kind == "oe":
+            toks = self._words(g, int(torch.randint(3, max(4, S), (1,), generator=g)))[:S - 1]
+            ids = [self.cls_id] + toks + [QA_TOK["answer"], QA_TOK[":"], self.mask_id] + [self.sep_id] + [self.pad_id] * (S - len(toks))
+            ans = int(torch.randint(1000, self.hi, (1,), generator=g))
+        else:
+            toks = self._words(g, int(torch.randint(3, 9, (1,), generator=g)))
+            for o in range(self.size_option):
+                toks += [QA_TOK["option"], QA_TOK["0"] + o, QA_TOK[":"]] + self._words(g, int(torch.randint(1, 5, (1,), generator=g)))
+            toks = toks[:S - 1]
+            ids = [self.cls_id] + toks + [self.mask_id] + [self.sep_id] + [self.pad_id] * (S - len(toks))
+            ans_idx = int(torch.randint(0, self.size_option, (1,), generator=g))
+            ans = self.ans_tok_ids[ans_idx]
+        txt = torch.LongTensor(ids)
+        mask = (txt != self.pad_id).long()
+        mask_ans = torch.ones_like(txt) * -1
+        mask_ans[txt == self.mask_id] = ans
+        return txt, mask, mask_ans, ans_idx
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed(1 + 3 * i + {"train": 0, "val": 1, "test": 2}.get(self.split, 0))
+        img = torch.randn(int(self.args.size_frame), 3, int(self.args.size_img), int(self.args.size_img), generator=g)
+        txt, mask, mask_ans, ans_idx = self.text(i)
+        return (img, txt, mask, mask_ans) if self.kind == "oe" else (img, txt, mask, mask_ans, ans_idx)
+
+    def collate_batch(self, inputs):
+        cols = list(map(list, zip(*inputs)))
+        batch = {"img": torch.stack(cols[0], 0), "txt": torch.stack(cols[1], 0), "mask": torch.stack(cols[2], 0), "mask_ans": torch.stack(cols[3], 0)}
+        if self.kind == "mc":
+            batch["ans_idx"] = torch.LongTensor(cols[4])
+        return batch
+
+
+class StubTokenizer:
+    """the special tokens and the "true" / "false" ids of bert-base-uncased, for entry points that run on synthetic token ids"""
+    cls_token = "[CLS]"; sep_token = "[SEP]"; pad_token = "[PAD]"; mask_token = "[MASK]"; unk_token = "[UNK]"
+    ids = {"[PAD]": 0, "[UNK]": 100, "[CLS]": 101, "[SEP]": 102, "[MASK]": 103, "true": 2995, "false": 6270}
+
+    def convert_tokens_to_ids(self, toks):
+        return [self.ids[t] for t in toks]
+
+
+def synthetic_qa_loaders(args, tokzr, kind, n_steps, n_val, vocab, rank=0, world=1):
+    """(train, val, test) DataLoaders over SyntheticQA and the train sampler (None on one rank): n_steps batches per rank for training, n_val
+    samples each for validation and test"""
+    def dl(ds, train):
+        sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=train) if world > 1 else None
+        return torch.utils.data.DataLoader(ds, batch_size=args.size_batch, sampler=sampler, shuffle=train and sampler is None,
+                                           num_workers=args.n_workers, pin_memory=True, drop_last=train, collate_fn=ds.collate_batch), sampler
+    tr, sampler = dl(SyntheticQA(args, n_steps * args.size_batch * world, "train", tokzr, kind, vocab), True)
+    vl, _ = dl(SyntheticQA(args, n_val, "val", tokzr, kind, vocab), False)
+    ts, _ = dl(SyntheticQA(args, n_val, "test", tokzr, kind, vocab), False)
+    return tr, vl, ts, sampler

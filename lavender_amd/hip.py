@@ -830,3 +830,40 @@ def retrieval_rank(S, gt, out=None):
         out = torch.empty(nt, dtype=torch.int32, device=S.device)
     L.check(L.lib.lav_retrieval_rank(_s(), nt, nv, _p(S), _ld(S), _p(gt), _p(out)), "lav_retrieval_rank")
     return out
+
+
+# ---- video-QA read-out (csrc/qa.hip) ------------------------------------------------------------------------------------------------------
+ANSWER_MAX_CAND, ANSWER_MAX_SPLITS = 32, 16          # LAV_ANSWER_MAX_CAND, LAV_ANSWER_MAX_SPLITS
+# column ranges per row of lav_answer_readout (probe hook; every value gives identical outputs).  1: one workgroup per row, one launch.
+# Measured at (32 x 30522) back to back (profiles/r13_qa_bench.json): bf16 8.83 us at 1, 8.11 us at 8; fp32 10.41 / 8.25 us.  The
+# 0.7 us do not pay for the workspace allocation a split adds to a call whose host side costs 14-16 us: the default stays 1.
+ANSWER_SPLITS = int(_os_env("LAV_QA_SPLITS", "1"))
+
+
+def answer_readout(logits, V, labels, cand=(), splits=None, out=None):
+    """(pred, rank, choice), each (n,) int32 on the device, of the n rows of a (n, V) bf16 / fp32 logits view (lav_answer_readout: arg-max column,
+    number of columns sorting before the label, arg-max of the candidates' share of their sum).  labels: (n,) label columns, -1 = none -- a host
+    array (numpy / CPU tensor: checked against [0, V) by the entry, then uploaded -- a copy from pageable host memory, which the runtime stages
+    and which may wait for that staging, not for the kernels queued before it) or an int32 device tensor (the caller vouches
+    for its values).  cand: up to 32 token ids on the host.  out: a (3, n) int32 device tensor to write into."""
+    import numpy as np
+    assert logits.dim() == 2 and logits.stride(-1) == 1 and logits.dtype in (bf16, torch.float32), "logits: a (n, V) bf16 / fp32 view with unit column stride"
+    n, dev = logits.shape[0], logits.device
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == n
+        lab_dev, lab_host = labels, None
+    else:
+        lab_np = np.ascontiguousarray(labels.numpy() if isinstance(labels, torch.Tensor) else labels, dtype=np.int32).reshape(-1)
+        assert lab_np.size == n, (lab_np.size, n)
+        lab_dev, lab_host = torch.from_numpy(lab_np).to(dev, non_blocking=True), lab_np.ctypes.data_as(C.c_void_p)
+    cand_np = np.ascontiguousarray(list(cand), dtype=np.int32)
+    splits = ANSWER_SPLITS if splits is None else int(splits)
+    if out is None:
+        out = torch.empty((3, n), dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.shape == (3, n) and out.is_contiguous()
+    need = int(L.lib.lav_answer_readout_workspace_bytes(n, splits))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    L.check(L.lib.lav_answer_readout(_s(), n, int(V), _p(logits), _ld(logits), int(logits.dtype == torch.float32), _p(lab_dev), lab_host,
+                                     cand_np.ctypes.data_as(C.c_void_p) if cand_np.size else None, int(cand_np.size), splits, _p(ws), need,
+                                     _p(out[0]), _p(out[1]), _p(out[2])), "lav_answer_readout")
+    return out[0], out[1], out[2]

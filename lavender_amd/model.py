@@ -219,28 +219,37 @@ class LAVENDER_Base(nn.Module):
             return mask
         return torch.cat([full_mask, mask_txt], dim=1)
 
-    def _encode(self, feat, mask, causal_from=0, pair=None):
-        """feat (n, L, H) bf16, mask (n, L) 0/1 key mask -> last_hidden_state (n, L, H).  causal_from > 0: seq2seq mask with that
-        many prefix (video) keys (lav_attn_desc.causal_from).  pair = (rowmap, start, order): feat is the UN-EXPANDED (U, H) source
-        and the first layer reads it through the pair map (engine.BertLayerFn)."""
+    def _layers(self, x, km, n, L, causal_from=0, pair=None, stop=None):
+        """The fusion encoder's layers [0, stop) (all of them by default) on x ((n * L, H) bf16 rows, or the un-expanded pair source with pair),
+        km the (n, L) int32 key mask: (x, x32) as the next layer takes them -- x32 is None, the fp32 copy, or with engine.RESLN the tuple
+        (pre, mean, rstd, gamma, beta) of the LayerNorm that produced x.  Dropout follows self.training.  The one layer loop of _encode,
+        LAVENDER_RetrievalMlmEval.score_pairs and LAVENDER_QAOE_MLM.answer_rows."""
         arena = self.arena()
-        arena.sync_half_if_stale()                            # e.g. load_ckpt followed directly by a 'cross' call on cached features
-        n, L = mask.shape
-        Hd = feat.shape[-1]
-        km = mask.to(torch.int32).contiguous()
-        x = feat.reshape(-1, Hd)
-        if not x.is_contiguous():
-            x = x.contiguous()
         ph = self.config.hidden_dropout_prob if self.training else 0.0
         pa = self.config.attention_probs_dropout_prob if self.training else 0.0
-        x32, last = None, len(self.trsfr.layer) - 1
-        for i, lyr in enumerate(self.trsfr.layer):
+        layers = self.trsfr.layer
+        x32, last = None, len(layers) - 1
+        for i, lyr in enumerate(layers[:stop]):
             out = E.BertLayerFn.apply(arena.anchor, x, x32, lyr, km, n, L, ph, pa, i < last, int(causal_from), pair if i == 0 else None)
             if len(out) == 4:                                 # engine.RESLN: the next residual add normalises this layer's pre-LN rows itself
                 ln = lyr.output.LayerNorm
                 x, x32 = out[0], (out[1], out[2], out[3], ln.weight.data, ln.bias.data)
             else:
                 x, x32 = out
+        return x, x32
+
+    def _encode(self, feat, mask, causal_from=0, pair=None):
+        """feat (n, L, H) bf16, mask (n, L) 0/1 key mask -> last_hidden_state (n, L, H).  causal_from > 0: seq2seq mask with that
+        many prefix (video) keys (lav_attn_desc.causal_from).  pair = (rowmap, start, order): feat is the UN-EXPANDED (U, H) source
+        and the first layer reads it through the pair map (engine.BertLayerFn)."""
+        self.arena().sync_half_if_stale()                     # e.g. load_ckpt followed directly by a 'cross' call on cached features
+        n, L = mask.shape
+        Hd = feat.shape[-1]
+        km = mask.to(torch.int32).contiguous()
+        x = feat.reshape(-1, Hd)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        x, _ = self._layers(x, km, n, L, causal_from, pair)
         return x.view(n, L, Hd)
 
     def _pair_source(self, feat_img, feat_txt, vi, ti):

@@ -217,14 +217,7 @@ class LAVENDER_RetrievalMlmEval(LAVENDER_Retrieval_MLM):
             x, pair = K.gather_rows(src.src, up(flat), n * L, Hd), None
         layers = self.trsfr.layer
         last = len(layers) - 1
-        x32 = None
-        for i, lyr in enumerate(layers[:last]):            # model._encode's layer loop (eval: no dropout)
-            o = E.BertLayerFn.apply(arena.anchor, x, x32, lyr, km, n, L, 0.0, 0.0, True, 0, pair if i == 0 else None)
-            if len(o) == 4:
-                ln = lyr.output.LayerNorm
-                x, x32 = o[0], (o[1], o[2], o[3], ln.weight.data, ln.bias.data)
-            else:
-                x, x32 = o
+        x, x32 = self._layers(x, km, n, L, pair=pair, stop=last)   # model._encode's layer loop (eval: no dropout), all but the last layer
         first = pair if last == 0 else None
         q = Lv + src.q_row[ti]                              # the [MASK] row of every pair within its sequence
         tid_true, tid_false = int(self.true_token_id), int(self.false_token_id)
