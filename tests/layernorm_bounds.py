@@ -108,7 +108,7 @@ def bwd(f, x, dy, gamma, add_in=None, row_scale=None, keep=None, want_dx2=False,
         dx = dx + add_in
     e_dx = e_dx + U32 * dx.abs()
     s_dx = rstd[:, None] * (e_m1[:, None] + m2.abs()[:, None] * e_xh + xh.abs() * e_m2[:, None]) + rho[:, None] * (dx - (add_in if add_in is not None else 0)).abs()
-    r = dict(dx=dx, b_dx=e_dx + U_BF * (dx.abs() + e_dx), m_dx=bfr(dx), s_dx=s_dx, R=R)
+    r = dict(dx=dx, e_dx=e_dx, b_dx=e_dx + U_BF * (dx.abs() + e_dx), m_dx=bfr(dx), s_dx=s_dx, R=R)          # e_dx: before the store (tests/embed_bounds.py)
     r["dgamma"] = (dy * xh).sum(0)
     r["b_dgamma"] = (dy.abs() * e_xh + U32 * (dy * xh).abs()).sum(0) + gam(R) * (dy * xh).abs().sum(0)
     r["dbeta"] = dy.sum(0)
