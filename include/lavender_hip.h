@@ -160,9 +160,9 @@ typedef struct lav_gemm_launch_info {
 int lav_gemm_plan(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits,
                   lav_gemm_launch_info* out, int max_out);
 int lav_gemm_tn_grouped_plan(int n_jobs, const lav_gemm_tn_job* jobs, int splits, lav_gemm_launch_info* out, int max_out);
-/* Same kind of hook for the large-window attention kernels (windows of 257 ... 768 tokens, attention_winl.hip): parts = 0 lets the library split
- * a problem into query parts by its own rule (the default), 1 / 3 force that many, -1 routes large windows to the generic kernels (tests compare
- * the two).  Process-wide; returns the previous value. */
+/* Same kind of hook for the large-window attention kernels (windows of up to 768 tokens without the precomputed tables, attention_winl.hip): parts = 0
+ * lets the library split a problem into query parts by its own rule (the default), 1 / 3 force that many, -1 routes large windows to the generic
+ * kernels (tests compare the two).  Process-wide; returns the previous value. */
 int lav_winl_select(int parts);
 
 /* ---------------------------------------------------------------------------------------------
@@ -289,7 +289,7 @@ int lav_attention_fwd(void* stream, const lav_attn_desc* d, const void* qkv, voi
 /* dqkv: bf16 same layout as qkv (fully written).  dbias_table: fp32, atomically accumulated (window mode). */
 int lav_attention_bwd(void* stream, const lav_attn_desc* d, const void* qkv, const void* out, const void* dout,
                       const float* lse, void* dqkv, float* dbias_table);
-/* Window mode, N <= 256 with the precomputed tables or 256 < N <= 768 (lav_attention_bias_split(d) == 1): the bias-table gradient
+/* Window mode, N <= 256 with the precomputed tables or N <= 768 without them (lav_attention_bias_split(d) == 1): the bias-table gradient
  * ALONE.  Call lav_attention_bwd with dbias_table = NULL first (it leaves delta behind the lse in the lse buffer), then this on any stream ordered after it --
  * the table gradient is a parameter gradient and does not have to sit in the dy -> dx chain (the reference computes it inside
  * autograd of video_swin.py:153-160). */
@@ -299,6 +299,20 @@ int lav_attention_bwd_bias(void* stream, const lav_attn_desc* d, const void* qkv
  * lav_attention_bwd has to produce it (sequence mode has none; windows of more than 768 tokens use the generic kernels). */
 int lav_attention_bias_split(const lav_attn_desc* d);
 size_t lav_attention_lse_elems(const lav_attn_desc* d);
+/* Probe hook, not part of the contract: the launches an attention entry would make for a descriptor, in order, without making them (no device is
+ * needed; tests/ assert the route they exercise).  pass: 0 = lav_attention_fwd, 1 = lav_attention_bwd with dbias_table = NULL, 2 = with a table,
+ * 3 = lav_attention_bwd_bias.  Pointers of the descriptor are only tested for presence.  Writes at most max_out entries and returns the number of
+ * launches (1 ... 3), or the error code the entry itself would return for the descriptor. */
+typedef struct lav_attn_launch_info {
+    const char* kernel;           /* the kernel's name without template arguments, e.g. "win_bwd1" */
+    const char* route;            /* "window persistent", "window large", "sequence one-image", "sequence chunked", "generic window", "generic sequence" */
+    unsigned grid_x, grid_y, block;   /* workgroups, threads per workgroup */
+    unsigned lds_bytes;           /* dynamic LDS of the launch */
+    int split;                    /* the kernel's partition scalar: batch slices (win_*), query parts (winl_fwd / dq / dkv), window slices (winl_dbias),
+                                     8-tile parts (seql_*), tile rounds per wave (generic kernels); 0 = none */
+    int delta_negated;            /* 1: the route's backward leaves -delta behind the lse (window persistent), 0: +delta */
+} lav_attn_launch_info;
+int lav_attention_plan(const lav_attn_desc* d, int pass, lav_attn_launch_info* out, int max_out);
 /* Fills d->comb and d->combT (each n_types*heads*8*8*64*16 bf16) from the current bias table: value(q,k) =
  * table[index(q,k), head] + (region(q) != region(k) ? -100 : 0), -30000 for padded keys (video_swin.py:153-160). */
 int lav_attention_build_bias(void* stream, const lav_attn_desc* d);
@@ -799,8 +813,7 @@ int lav_answer_readout(void* stream, int n, int V, const void* logits, long ld, 
  *   stored non-temporally, bit 2: loaded non-temporally; by lav_adamw_step, default 1 -- bit 1: non-temporal parameter / moment
  *   stores), LAV_GEMM_DBG (timing ablations of the 256x256 kernel: WRONG results),
  *   LAV_LN_ATOMIC_FLUSH (LayerNorm backward column sums by per-block atomics), LAV_LN_G32 (bit 0 / bit 1: 32-lane x 3-chunk rows for C = 768 in the
- *   forward / backward, default 1), LAV_WIN_BWD1 (0: window attention backward as the two
- *   round-3 passes instead of the one-pass kernel), LAV_WINL / LAV_SEQL (0: large windows / long sequences on the generic kernels).
+ *   forward / backward, default 1), LAV_WINL / LAV_SEQL (0: large windows / long sequences on the generic kernels).
  * lav_gemm_select(which, value) changes these GEMM ones at run time (same caveat: process-wide, for probes): 2 = LAV_GEMM_PP_TN, 5 = LAV_GEMM_DBG,
  * 6 = LAV_GEMM_GROUP_N, 7 = LAV_GEMM_H192, 9 = LAV_GEMM_H192L, 11 = LAV_GEMM_PS, 12 = LAV_GEMM_TN_MINM; the others (LAV_GEMM_TN_KIND,
  * LAV_GEMM_TN_GROUP, LAV_NT_STORES) are fixed when the library is loaded.

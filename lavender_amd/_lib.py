@@ -67,6 +67,11 @@ class AttnDesc(C.Structure):
                 ("n_types", i32), ("comb", vp), ("combT", vp), ("causal_from", i32), ("qkv_headmajor", i32), ("bias_map", vp)]
 
 
+class AttnLaunchInfo(C.Structure):        # struct lav_attn_launch_info (lav_attention_plan)
+    _fields_ = [("kernel", C.c_char_p), ("route", C.c_char_p), ("grid_x", u32), ("grid_y", u32), ("block", u32), ("lds_bytes", u32), ("split", i32),
+                ("delta_negated", i32)]
+
+
 class BertLayerDesc(C.Structure):          # struct lav_bert_layer_desc (stage-level entries)
     _fields_ = ([(n, i32) for n in ("n_seq", "L", "hidden", "heads", "ffn")] + [(n, f32) for n in ("p_hidden", "p_attn", "ln_eps")] +
                 [(n, u32) for n in ("seed_attn", "seed1", "seed2")] + [("causal_from", i32)] +
@@ -175,6 +180,7 @@ _SIGS = {
     "lav_attention_bwd_bias": (i32, [vp, P(AttnDesc), vp, vp, vp, vp]),
     "lav_attention_bias_split": (i32, [P(AttnDesc)]),
     "lav_attention_lse_elems": (C.c_size_t, [P(AttnDesc)]),
+    "lav_attention_plan": (i32, [P(AttnDesc), i32, P(AttnLaunchInfo), i32]),
     "lav_attention_build_bias_map": (i32, [vp, P(AttnDesc)]),
     "lav_attention_build_bias": (i32, [vp, P(AttnDesc)]),
     "lav_patch_im2col": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -10,6 +10,7 @@
 // as a B operand straight from registers.  K sits in LDS swizzled for ds_read_b128 A-fragments; V sits
 // row-major and is read with ds_read_b64_tr_b16 (hardware transpose) as the A operand of O^T = V^T P^T.
 #include "attn_common.h"
+#include <stdlib.h>
 
 #define LOG2E 1.4426950408889634f
 
@@ -693,123 +694,183 @@ extern "C" size_t lav_attention_lse_elems(const lav_attn_desc* d) {
     return (size_t)2 * problems * d->heads * a.Npad;      // lse followed by delta (backward scratch)
 }
 
-template <typename K>
-static void set_lds(K kern, size_t bytes) {
-    if (bytes > 65536) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); (void)hipGetLastError(); }
+// ---- switches: read from the environment once, when the library is loaded; lav_winl_select changes the query parts at run time -----------------
+static bool env_on(const char* v) { return v ? atoi(v) != 0 : true; }
+static AttnSwitches attn_sw = {env_on(getenv("LAV_WINL")), env_on(getenv("LAV_SEQL")), 0};
+// test hook: force the number of query parts per large-window problem (0 = by problem count, -1 = large windows on the generic kernels)
+extern "C" int lav_winl_select(int parts) { const int old = attn_sw.winl_parts; attn_sw.winl_parts = parts; return old; }
+
+// ---- route plan: pure, the CPU tests call it through lav_attention_plan -------------------------------------------------------------------
+static WlTab wl_tab(const AttnArgs& a) {
+    const lav_attn_desc& d = a.d;
+    const int i = a.N - 1;                                   // codes grow with the slot index: the last slot has the largest
+    WlTab t;
+    t.mc = (i / (d.cfg_wh * d.cfg_ww)) * a.cstride_d + ((i / d.cfg_ww) % d.cfg_wh) * a.cstride_h + (i % d.cfg_ww);
+    t.lo = a.tbl_const - t.mc;
+    t.n = 2 * t.mc + 1;
+    return t;
+}
+// persistent kernels: batch slices per (head, window position[, key half]) so that ~256 workgroups exist
+static int pick_bsplit(const AttnArgs& a, int per_pair) {
+    const int base = a.d.heads * a.nWs * per_pair;
+    int bs = (256 + base - 1) / base;
+    if (bs > a.d.B) bs = a.d.B;
+    if (bs < 1) bs = 1;
+    return bs;
 }
 
-#define WIN_KL 256
-#define SEQ_KL_FWD 288   // forward: K/V of a whole fusion sequence (L <= 288) staged once, two blocks per CU
-#define SEQ_KL 128       // backward dQ pass: 128-key chunks -> 48 KB of LDS, the register file (not LDS) sets the occupancy
+AttnPlan attn_plan(const AttnArgs& a, int problems, const AttnSwitches& sw) {
+    const lav_attn_desc& d = a.d;
+    AttnPlan p;
+    memset(&p, 0, sizeof(p));
+    p.NT = a.nqt;
+    const unsigned nprob = (unsigned)(problems * d.heads);
+    auto put = [&p](int pass, int kern, unsigned gx, unsigned gy, unsigned block, size_t lds, int split) {
+        p.launch[pass][p.n[pass]++] = {kern, gx, gy, block, lds, split};
+    };
+    auto walk = [](unsigned items, unsigned cap) { return items < cap ? items : cap; };   // workgroups of a kernel that walks its items
+    bool large = false, chunked = false;
+    if (d.mode == 0 && !d.comb && sw.winl && sw.winl_parts >= 0 && a.N <= WL_ROWS) {
+        p.tab = wl_tab(a);
+        const double qkv_bytes = (double)d.B * a.tps * 3.0 * a.C * 2.0;             // DMA offsets are 32-bit
+        large = qkv_bytes < 4.0e9 && p.tab.lo >= 0 && p.tab.lo + p.tab.n <= a.tbl_rows &&
+                (size_t)p.tab.n * 4 + 2 * WL_IMG + 5 * WL_ROWS * 4 + 512 <= 160 * 1024 && (size_t)p.tab.n * 4 + WLB_MAIN + 384 * 4 + 512 <= 160 * 1024;
+    }
+    if (d.mode == 1 && a.N > SEQ3_ROWS)     // (32-bit DMA offsets per problem base are fine; keep the whole tensor below 4 GB anyway)
+        chunked = sw.seql && a.N <= SEQL_ROWS && (double)d.n_seq * a.N * 3.0 * a.C * 2.0 < 4.0e9;
 
-extern "C" int lav_attention_fwd(void* stream, const lav_attn_desc* d, const void* qkv, void* out, float* lse) {
-    AttnArgs a; int problems = 0;
-    if (int rc = attn_setup(d, a, problems)) return rc;
-    LAV_REQUIRE(qkv && out, "lav_attention_fwd: null pointer");
-    LAV_REQUIRE(!d->qkv_headmajor || (d->mode == 0 && d->comb && d->head_dim == 32), "lav_attention_fwd: qkv_headmajor needs window mode with the precomputed tables (N <= 256, head_dim 32)");
-    // head-major operand offsets are 32-bit byte offsets from the first token row: [q | k | v][head] planes of the WHOLE batch
-    LAV_REQUIRE(!d->qkv_headmajor || 6L * d->heads * d->head_dim * d->B * d->D * d->H * d->W < (1L << 32), "lav_attention_fwd: head-major qkv of %ld bytes exceeds the 4 GiB the window kernels address with 32-bit offsets",
-                6L * d->heads * d->head_dim * d->B * d->D * d->H * d->W);
-    a.qkv = (const bf16_t*)qkv; a.o_w = (bf16_t*)out; a.lse = lse;
-    if (d->mode == 0 && d->comb) return win_persistent_fwd(stream, a);
-    if (winl_supported(a)) return winl_fwd_launch(stream, a, problems);
-    if (seq3_supported(a)) return seq3_fwd(stream, a, problems);
-    hipStream_t s = (hipStream_t)stream;
-    const int KL = d->mode == 0 ? WIN_KL : SEQ_KL_FWD;
-    const int qgroups = (a.nqt + 3) / 4;
-    if (a.N <= KL) { a.R = qgroups; } else { a.R = 1; }
-    dim3 grid(problems * d->heads, a.N <= KL ? 1 : qgroups), block(256);
-    if (d->mode == 0) {
-        size_t lds = (size_t)WIN_KL * 32 * 2 * 2 + WIN_KL * 4 + (size_t)a.tbl_rows * 4;
-        set_lds(attn_fwd_kernel<32, 0, 8, WIN_KL>, lds);
-        hipLaunchKernelGGL((attn_fwd_kernel<32, 0, 8, WIN_KL>), grid, block, lds, s, a);
-    } else {
-        size_t lds = (size_t)SEQ_KL_FWD * 64 * 2 * 2 + SEQ_KL_FWD * 4;
-        if (d->causal_from > 0) {
-            set_lds(attn_fwd_kernel<64, 1, 3, SEQ_KL_FWD, true>, lds);
-            hipLaunchKernelGGL((attn_fwd_kernel<64, 1, 3, SEQ_KL_FWD, true>), grid, block, lds, s, a);
+    if (d.mode == 0 && d.comb) {                             // N <= 256 with the fragment tables (attention_win.hip)
+        p.route = AR_WIN_PERSISTENT; p.bias_split = true; p.delta_negated = true;
+        const int bs = pick_bsplit(a, 1), bsb = pick_bsplit(a, 2);
+        const unsigned grid = (unsigned)(d.heads * a.nWs * bs);
+        put(AP_FWD, AK_WIN_FWD3, grid, 1, 512, 2 * 49152 + 1024, bs);
+        put(AP_BWD, AK_WIN_BWD1, grid, 1, 512, 2 * (32768 + 1024) + 1024 + 8 * 6144 + 8 * 4096 + 1024 + 64, bs);
+        put(AP_BIAS, AK_WIN_DBIAS3, (unsigned)(d.heads * a.nWs * bsb * 2), 1, 512, 128 * 257 * 4 + 1024, bsb);   // max(two operand buffers, the flush matrix) + token rows
+    } else if (large) {                                      // N <= 768 without them (attention_winl.hip)
+        p.route = AR_WIN_LARGE; p.bias_split = true;
+        const int QS = sw.winl_parts > 0 ? sw.winl_parts : nprob >= 1024 ? 1 : 3;
+        const unsigned grid = walk(nprob * QS, 256);
+        const size_t lds = 2 * WL_IMG + 3 * WL_ROWS * 4 + (size_t)p.tab.n * 4;
+        put(AP_FWD, AK_WINL_FWD, grid, 1, 512, lds, QS);
+        put(AP_BWD, AK_WINL_DQ, grid, 1, 512, lds, QS);
+        put(AP_BWD, AK_WINL_DKV, grid, 1, 512, lds + 2 * WL_ROWS * 4, QS);
+        const int nqb = (a.nqt + 3) / 4, nkb = (a.nqt + 7) / 8, base = d.heads * nqb * nkb;
+        int WS = (512 + base - 1) / base;
+        if (WS > problems) WS = problems;
+        if (WS < 1) WS = 1;
+        put(AP_BIAS, AK_WINL_DBIAS, (unsigned)(base * WS), 1, 512, WLB_MAIN + 384 * 4 + (size_t)p.tab.n * 4, WS);
+    } else if (chunked) {                                    // 288 < L <= 768 (attention_seq.hip, second half)
+        p.route = AR_SEQ_CHUNKED;
+        const int parts = (a.nqt + 7) / 8;
+        const unsigned grid = walk(nprob * parts, 256);
+        put(AP_FWD, AK_SEQL_FWD, grid, 1, 512, 2 * SEQL_BUF + SEQL_ROWS * 4, parts);
+        put(AP_BWD, AK_SEQL_DQ, grid, 1, 512, 2 * SEQL_BUF + SEQL_ROWS * 4, parts);
+        put(AP_BWD, AK_SEQL_DKV, grid, 1, 512, 2 * SEQL_BUF + SEQL_ROWS * 8, parts);
+    } else if (d.mode == 1 && a.N <= SEQ3_ROWS) {            // L <= 288 (attention_seq.hip)
+        p.route = AR_SEQ_ONE;
+        const unsigned grid = walk(nprob, 512);
+        put(AP_FWD, AK_SEQ_FWD3, grid, 1, 256, 2 * SEQ3_IMG + SEQ3_ROWS * 4, 0);
+        put(AP_BWD, AK_SEQ_DQ3, grid, 1, 256, 2 * SEQ3_IMG + SEQ3_ROWS * 4, 0);
+        put(AP_BWD, AK_SEQ_DKV3, grid, 1, 256, 2 * SEQ3_IMG + SEQ3_ROWS * 8, 0);
+    } else {                                                 // the generic kernels of this file
+        p.route = d.mode == 0 ? AR_GEN_WINDOW : AR_GEN_SEQ;
+        const int qgroups = (a.nqt + 3) / 4;
+        // a problem whose keys / queries fit one staged chunk takes one workgroup (R tile rounds per wave), else one per group of four tiles
+        auto gen = [&](int pass, int kern, int chunk, size_t lds) {
+            const bool one = a.N <= chunk;
+            put(pass, kern, nprob, one ? 1 : qgroups, 256, lds, one ? qgroups : 1);
+        };
+        if (d.mode == 0) {
+            gen(AP_FWD, AK_GEN_FWD, WIN_KL, (size_t)WIN_KL * 32 * 2 * 2 + WIN_KL * 4 + (size_t)a.tbl_rows * 4);
+            gen(AP_BWD, AK_GEN_DQ, WIN_KL, (size_t)WIN_KL * 32 * 2 * 3 + WIN_KL * 4 + (size_t)a.tbl_rows * 8);
+            gen(AP_BWD, AK_GEN_DKV, WIN_KL, (size_t)WIN_KL * 32 * 2 * 4 + WIN_KL * 12 + (size_t)a.tbl_rows * 4);
         } else {
-            set_lds(attn_fwd_kernel<64, 1, 3, SEQ_KL_FWD>, lds);
-            hipLaunchKernelGGL((attn_fwd_kernel<64, 1, 3, SEQ_KL_FWD>), grid, block, lds, s, a);
+            gen(AP_FWD, AK_GEN_FWD, SEQ_KL_FWD, (size_t)SEQ_KL_FWD * 64 * 2 * 2 + SEQ_KL_FWD * 4);
+            gen(AP_BWD, AK_GEN_DQ, SEQ_KL, (size_t)SEQ_KL * 64 * 2 * 3 + SEQ_KL * 4);
+            gen(AP_BWD, AK_GEN_DKV, SEQ_QL, (size_t)SEQ_QL * 64 * 2 * 4 + SEQ_QL * 12);
         }
     }
-    return lav_check_launch("lav_attention_fwd");
+    // backward with the bias-table gradient: the split routes append their bias launch; the generic dQ kernel accumulates it itself (a.dbias)
+    for (int i = 0; i < p.n[AP_BWD]; ++i) p.launch[AP_BWD_BIAS][p.n[AP_BWD_BIAS]++] = p.launch[AP_BWD][i];
+    if (p.bias_split) p.launch[AP_BWD_BIAS][p.n[AP_BWD_BIAS]++] = p.launch[AP_BIAS][0];
+    return p;
 }
 
-#define SEQ_QL 128       // backward dK/dV pass: 128-query chunks (4 staged copies = 64 KB): two blocks per CU instead of one
+// ---- launches ---------------------------------------------------------------------------------------------------------------------------
+template <bool CAUSAL>
+static void gen_seq_launch(hipStream_t s, const AttnArgs& a, const AttnLaunch& l, float* delta) {
+    switch (l.kern) {
+    case AK_GEN_FWD: attn_launch(attn_fwd_kernel<64, 1, 3, SEQ_KL_FWD, CAUSAL>, l, s, a); break;
+    case AK_GEN_DQ: attn_launch(attn_bwd_dq_kernel<64, 1, SEQ_KL, CAUSAL>, l, s, a, delta); break;
+    default: attn_launch(attn_bwd_dkv_kernel<64, 1, SEQ_QL, CAUSAL>, l, s, a, delta); break;
+    }
+}
+static void gen_launch(hipStream_t s, AttnArgs& a, const AttnLaunch& l, float* delta) {
+    a.R = l.split;
+    if (a.d.mode == 1) { if (a.d.causal_from > 0) gen_seq_launch<true>(s, a, l, delta); else gen_seq_launch<false>(s, a, l, delta); return; }
+    switch (l.kern) {
+    case AK_GEN_FWD: attn_launch(attn_fwd_kernel<32, 0, 8, WIN_KL>, l, s, a); break;
+    case AK_GEN_DQ: attn_launch(attn_bwd_dq_kernel<32, 0, WIN_KL>, l, s, a, delta); break;
+    default: attn_launch(attn_bwd_dkv_kernel<32, 0, WIN_KL>, l, s, a, delta); break;
+    }
+}
+
+// every launch of one pass of the plan, in order; delta = the scratch behind the lse
+static int attn_run(void* stream, AttnArgs& a, int problems, const AttnPlan& p, int pass, const char* entry) {
+    hipStream_t s = (hipStream_t)stream;
+    float* delta = a.lse ? a.lse + (size_t)problems * a.d.heads * a.Npad : nullptr;
+    for (int i = 0; i < p.n[pass]; ++i) {
+        const AttnLaunch& l = p.launch[pass][i];
+        if (l.kern <= AK_WIN_DBIAS3) win_launch(s, a, p, l, delta);
+        else if (l.kern <= AK_WINL_DBIAS) winl_launch(s, a, p, l, delta);
+        else if (l.kern <= AK_SEQL_DKV) seq_launch(s, a, p, l, delta);
+        else gen_launch(s, a, l, delta);
+    }
+    return lav_check_launch(entry);
+}
+
+// ---- entries ----------------------------------------------------------------------------------------------------------------------------
+// descriptor checks, the operand-layout checks every entry shares, and the plan
+static int attn_prepare(const lav_attn_desc* d, const char* entry, AttnArgs& a, int& problems, AttnPlan& p) {
+    if (int rc = attn_setup(d, a, problems)) return rc;
+    LAV_REQUIRE(!d->qkv_headmajor || (d->mode == 0 && d->comb && d->head_dim == 32), "%s: qkv_headmajor needs window mode with the precomputed tables (N <= 256, head_dim 32)", entry);
+    // head-major operand offsets are 32-bit byte offsets from the first token row: [q | k | v][head] planes of the WHOLE batch
+    const long hm_bytes = 6L * d->heads * d->head_dim * d->B * d->D * d->H * d->W;
+    LAV_REQUIRE(!d->qkv_headmajor || hm_bytes < (1L << 32), "%s: head-major qkv of %ld bytes exceeds the 4 GiB the window kernels address with 32-bit offsets", entry, hm_bytes);
+    p = attn_plan(a, problems, attn_sw);
+    return LAV_OK;
+}
+
+extern "C" int lav_attention_fwd(void* stream, const lav_attn_desc* d, const void* qkv, void* out, float* lse) {
+    AttnArgs a; int problems = 0; AttnPlan p;
+    LAV_REQUIRE(qkv && out, "lav_attention_fwd: null pointer");
+    if (int rc = attn_prepare(d, "lav_attention_fwd", a, problems, p)) return rc;
+    a.qkv = (const bf16_t*)qkv; a.o_w = (bf16_t*)out; a.lse = lse;
+    return attn_run(stream, a, problems, p, AP_FWD, "lav_attention_fwd");
+}
 
 extern "C" int lav_attention_bwd(void* stream, const lav_attn_desc* d, const void* qkv, const void* out, const void* dout,
                                  const float* lse, void* dqkv, float* dbias_table) {
-    AttnArgs a; int problems = 0;
-    if (int rc = attn_setup(d, a, problems)) return rc;
+    AttnArgs a; int problems = 0; AttnPlan p;
     LAV_REQUIRE(qkv && out && dout && lse && dqkv, "lav_attention_bwd: null pointer");
-    LAV_REQUIRE(!d->qkv_headmajor || (d->mode == 0 && d->comb && d->head_dim == 32), "lav_attention_bwd: qkv_headmajor needs window mode with the precomputed tables (N <= 256, head_dim 32)");
-    // head-major operand offsets are 32-bit byte offsets from the first token row: [q | k | v][head] planes of the WHOLE batch
-    LAV_REQUIRE(!d->qkv_headmajor || 6L * d->heads * d->head_dim * d->B * d->D * d->H * d->W < (1L << 32), "lav_attention_bwd: head-major qkv of %ld bytes exceeds the 4 GiB the window kernels address with 32-bit offsets",
-                6L * d->heads * d->head_dim * d->B * d->D * d->H * d->W);
+    if (int rc = attn_prepare(d, "lav_attention_bwd", a, problems, p)) return rc;
     a.qkv = (const bf16_t*)qkv; a.out = (const bf16_t*)out; a.dout = (const bf16_t*)dout; a.lse = (float*)lse;
     a.dqkv = (bf16_t*)dqkv; a.dbias = dbias_table;
-    float* delta = (float*)lse + (size_t)problems * d->heads * a.Npad;
-    if (d->mode == 0 && d->comb) return win_persistent_bwd(stream, a, delta);
-    if (winl_supported(a)) return winl_bwd_launch(stream, a, problems, delta);
-    if (seq3_supported(a)) return seq3_bwd(stream, a, problems, delta);
-    hipStream_t s = (hipStream_t)stream;
-    const int qgroups = (a.nqt + 3) / 4;
-    if (d->mode == 0) {
-        const bool one = a.N <= WIN_KL;
-        a.R = one ? qgroups : 1;
-        dim3 grid(problems * d->heads, one ? 1 : qgroups), block(256);
-        size_t lds1 = (size_t)WIN_KL * 32 * 2 * 3 + WIN_KL * 4 + (size_t)a.tbl_rows * 8;
-        set_lds(attn_bwd_dq_kernel<32, 0, WIN_KL>, lds1);
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<32, 0, WIN_KL>), grid, block, lds1, s, a, delta);
-        size_t lds2 = (size_t)WIN_KL * 32 * 2 * 4 + WIN_KL * 12 + (size_t)a.tbl_rows * 4;
-        set_lds(attn_bwd_dkv_kernel<32, 0, WIN_KL>, lds2);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, 0, WIN_KL>), grid, block, lds2, s, a, (const float*)delta);
-    } else {
-        const bool one = a.N <= SEQ_KL;
-        a.R = one ? qgroups : 1;
-        dim3 grid(problems * d->heads, one ? 1 : qgroups), block(256);
-        size_t lds1 = (size_t)SEQ_KL * 64 * 2 * 3 + SEQ_KL * 4;
-        const bool causal = d->causal_from > 0;
-        if (causal) {
-            set_lds(attn_bwd_dq_kernel<64, 1, SEQ_KL, true>, lds1);
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 1, SEQ_KL, true>), grid, block, lds1, s, a, delta);
-        } else {
-            set_lds(attn_bwd_dq_kernel<64, 1, SEQ_KL>, lds1);
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 1, SEQ_KL>), grid, block, lds1, s, a, delta);
-        }
-        const bool one2 = a.N <= SEQ_QL;
-        a.R = one2 ? qgroups : 1;
-        dim3 grid2(problems * d->heads, one2 ? 1 : qgroups);
-        size_t lds2 = (size_t)SEQ_QL * 64 * 2 * 4 + SEQ_QL * 12;
-        if (causal) {
-            set_lds(attn_bwd_dkv_kernel<64, 1, SEQ_QL, true>, lds2);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 1, SEQ_QL, true>), grid2, block, lds2, s, a, (const float*)delta);
-        } else {
-            set_lds(attn_bwd_dkv_kernel<64, 1, SEQ_QL>, lds2);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 1, SEQ_QL>), grid2, block, lds2, s, a, (const float*)delta);
-        }
-    }
-    return lav_check_launch("lav_attention_bwd");
+    return attn_run(stream, a, problems, p, dbias_table ? AP_BWD_BIAS : AP_BWD, "lav_attention_bwd");
 }
 
 // Bias-table gradient alone (window mode; persistent N <= 256 path or large-window path): needs the forward's lse and the delta scratch that
-// lav_attention_bwd (called first, with dbias_table = NULL) left behind the lse in the same buffer -- stored NEGATED by the persistent
-// kernels (win_dq3 / win_bwd1: -delta is the C operand of their dP MFMAs), as +delta by the large-window ones (winl_dq).  A parameter
-// gradient: the engine issues it on the weight-gradient stream.
+// lav_attention_bwd (called first, with dbias_table = NULL) left behind the lse in the same buffer -- NEGATED on the persistent route (win_bwd1
+// writes -delta, the C operand of its dP MFMAs, and win_dbias3 reads it), +delta on the large-window one (winl_dq writes, winl_dbias reads):
+// AttnPlan.delta_negated.  A parameter gradient: the engine issues it on the weight-gradient stream.
 extern "C" int lav_attention_bwd_bias(void* stream, const lav_attn_desc* d, const void* qkv, const void* dout, const float* lse,
                                       float* dbias_table) {
-    AttnArgs a; int problems = 0;
-    if (int rc = attn_setup(d, a, problems)) return rc;
+    AttnArgs a; int problems = 0; AttnPlan p;
     LAV_REQUIRE(qkv && dout && lse && dbias_table, "lav_attention_bwd_bias: null pointer");
-    LAV_REQUIRE(!d->qkv_headmajor || (d->mode == 0 && d->comb && d->head_dim == 32), "lav_attention_bwd_bias: qkv_headmajor needs window mode with the precomputed tables (N <= 256, head_dim 32)");
-    // head-major operand offsets are 32-bit byte offsets from the first token row: [q | k | v][head] planes of the WHOLE batch
-    LAV_REQUIRE(!d->qkv_headmajor || 6L * d->heads * d->head_dim * d->B * d->D * d->H * d->W < (1L << 32), "lav_attention_bwd_bias: head-major qkv of %ld bytes exceeds the 4 GiB the window kernels address with 32-bit offsets",
-                6L * d->heads * d->head_dim * d->B * d->D * d->H * d->W);
+    if (int rc = attn_prepare(d, "lav_attention_bwd_bias", a, problems, p)) return rc;
+    LAV_REQUIRE(p.bias_split, "lav_attention_bwd_bias: window mode on the persistent (N <= 256, tables given) or large-window (N <= 768) path only");
     a.qkv = (const bf16_t*)qkv; a.dout = (const bf16_t*)dout; a.lse = (float*)lse; a.dbias = dbias_table;
-    if (d->mode == 0 && !d->comb && winl_supported(a)) return winl_dbias_launch(stream, a, problems, lse + (size_t)problems * d->heads * a.Npad);
-    LAV_REQUIRE(d->mode == 0 && d->comb, "lav_attention_bwd_bias: window mode on the persistent (N <= 256, tables given) or large-window (N <= 768) path only");
-    return win_persistent_dbias(stream, a, lse + (size_t)problems * d->heads * a.Npad);
+    return attn_run(stream, a, problems, p, AP_BIAS, "lav_attention_bwd_bias");
 }
 
 // 1 when the bias-table gradient of this descriptor can run as its own launch (lav_attention_bwd with dbias_table = NULL, then
@@ -817,6 +878,23 @@ extern "C" int lav_attention_bwd_bias(void* stream, const lav_attn_desc* d, cons
 extern "C" int lav_attention_bias_split(const lav_attn_desc* d) {
     AttnArgs a; int problems = 0;
     if (attn_setup(d, a, problems)) return 0;
-    return d->mode == 0 && (d->comb || winl_supported(a)) ? 1 : 0;
+    return attn_plan(a, problems, attn_sw).bias_split ? 1 : 0;
 }
 
+// probe hook: the launches the entry of `pass` would make for this descriptor, without making them (no device needed)
+extern "C" int lav_attention_plan(const lav_attn_desc* d, int pass, lav_attn_launch_info* out, int max_out) {
+    static const char* const kernels[AK_COUNT] = {"win_fwd3", "win_bwd1", "win_dbias3", "winl_fwd", "winl_dq", "winl_dkv", "winl_dbias", "seq_fwd3", "seq_dq3",
+                                                  "seq_dkv3", "seql_fwd", "seql_dq", "seql_dkv", "attn_fwd_kernel", "attn_bwd_dq_kernel", "attn_bwd_dkv_kernel"};
+    static const char* const routes[AR_COUNT] = {"window persistent", "window large", "sequence one-image", "sequence chunked", "generic window", "generic sequence"};
+    static const char* const entries[AP_COUNT] = {"lav_attention_fwd", "lav_attention_bwd", "lav_attention_bwd", "lav_attention_bwd_bias"};
+    LAV_REQUIRE(pass >= 0 && pass < AP_COUNT, "lav_attention_plan: pass %d (0 forward, 1 backward, 2 backward with the bias-table gradient, 3 that gradient alone)", pass);
+    LAV_REQUIRE(out || max_out <= 0, "lav_attention_plan: null output array");
+    AttnArgs a; int problems = 0; AttnPlan p;
+    if (int rc = attn_prepare(d, entries[pass], a, problems, p)) return rc;
+    LAV_REQUIRE(pass != AP_BIAS || p.bias_split, "lav_attention_bwd_bias: window mode on the persistent (N <= 256, tables given) or large-window (N <= 768) path only");
+    for (int i = 0; i < p.n[pass] && i < max_out; ++i) {
+        const AttnLaunch& l = p.launch[pass][i];
+        out[i] = {kernels[l.kern], routes[p.route], l.grid_x, l.grid_y, l.block, (unsigned)l.lds, l.split, p.delta_negated ? 1 : 0};
+    }
+    return p.n[pass];
+}

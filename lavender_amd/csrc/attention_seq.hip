@@ -14,12 +14,9 @@
 // Longer sequences (the 757-token Swin-L-384 shape, up to 768) run the chunked kernels at the end of this file; beyond that the generic
 // kernels of attention.hip.
 #include "attn_common.h"
-#include <stdlib.h>
 
 #define LOG2E 1.4426950408889634f
 #define HD 64
-#define SEQ3_ROWS 288                                      // LDS image rows
-#define SEQ3_IMG (SEQ3_ROWS * 128)
 
 __device__ __forceinline__ void sdma16(unsigned lds_dst, const void* sbase, unsigned voff) {
     unsigned keep_m0;
@@ -524,11 +521,6 @@ __global__ __launch_bounds__(256, 2) void seq_dkv3(AttnArgs a, int nprob, const 
 // in registers across the whole walk, and the other operand streams through LDS in 256-row chunks, double-buffered: chunk
 // c + 1 is in flight (global_load_lds) under chunk c's MFMAs.  LDS: [2][image A 32 KB | image B 32 KB] + per-row floats.
 // ======================================================================================================
-#define SEQL_ROWS 768
-#define SEQL_CH 256                                         // rows per chunk
-#define SEQL_IMG (SEQL_CH * 128)
-#define SEQL_BUF (2 * SEQL_IMG)
-
 // DMA of rows [row0, row0 + 256) of an operand (clamped to the last row of the sequence): 32 one-KB pieces, 4 per wave
 __device__ __forceinline__ void seql_dma_chunk(unsigned lds_img, const bf16_t* base, long ld, int L, int row0, int wave, int lane) {
 #pragma unroll
@@ -940,73 +932,21 @@ __global__ __launch_bounds__(512) void seql_dkv(AttnArgs a, int nprob, int parts
 }
 
 // ------------------------------------------------------------------------------------------------------
-template <typename Kn>
-static void seq_lds(Kn k, size_t bytes) {
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    (void)hipGetLastError();
-}
-
-static const bool lav_seql_on = getenv("LAV_SEQL") ? atoi(getenv("LAV_SEQL")) != 0 : true;   // probe hook: 0 = generic kernels for L > 288
-bool seq3_supported(const AttnArgs& a) {
-    if (a.d.mode != 1) return false;
-    if (a.N <= SEQ3_ROWS) return true;
-    return lav_seql_on && a.N <= SEQL_ROWS && (double)a.d.n_seq * a.N * 3.0 * a.C * 2.0 < 4.0e9;      // 32-bit DMA offsets per problem base are fine; keep the whole tensor below 4 GB anyway
-}
-
-#define SEQ3_DISPATCH(KERN, lds, ...)                                                                               \
-    do {                                                                                                            \
-        const bool causal = a.d.causal_from > 0, drop = a.d.dropout_p > 0.f;                                        \
-        if (causal) {                                                                                               \
-            if (drop) { seq_lds(KERN<true, true>, lds); hipLaunchKernelGGL((KERN<true, true>), grid, dim3(256), lds, s, __VA_ARGS__); }   \
-            else { seq_lds(KERN<true, false>, lds); hipLaunchKernelGGL((KERN<true, false>), grid, dim3(256), lds, s, __VA_ARGS__); }      \
-        } else {                                                                                                    \
-            if (drop) { seq_lds(KERN<false, true>, lds); hipLaunchKernelGGL((KERN<false, true>), grid, dim3(256), lds, s, __VA_ARGS__); } \
-            else { seq_lds(KERN<false, false>, lds); hipLaunchKernelGGL((KERN<false, false>), grid, dim3(256), lds, s, __VA_ARGS__); }    \
-        }                                                                                                           \
-    } while (0)
-
-#define SEQL_DISPATCH(KERN, lds, ...)                                                                               \
-    do {                                                                                                            \
-        const bool causal = a.d.causal_from > 0, drop = a.d.dropout_p > 0.f;                                        \
-        if (causal) {                                                                                               \
-            if (drop) { seq_lds(KERN<true, true>, lds); hipLaunchKernelGGL((KERN<true, true>), grid, dim3(512), lds, s, __VA_ARGS__); }   \
-            else { seq_lds(KERN<true, false>, lds); hipLaunchKernelGGL((KERN<true, false>), grid, dim3(512), lds, s, __VA_ARGS__); }      \
-        } else {                                                                                                    \
-            if (drop) { seq_lds(KERN<false, true>, lds); hipLaunchKernelGGL((KERN<false, true>), grid, dim3(512), lds, s, __VA_ARGS__); } \
-            else { seq_lds(KERN<false, false>, lds); hipLaunchKernelGGL((KERN<false, false>), grid, dim3(512), lds, s, __VA_ARGS__); }    \
-        }                                                                                                           \
-    } while (0)
-
-int seq3_fwd(void* stream, const AttnArgs& a, int problems) {
-    hipStream_t s = (hipStream_t)stream;
-    const int nprob = problems * a.d.heads;
-    if (a.N > SEQ3_ROWS) {
-        const int parts = (a.nqt + 7) / 8, items = nprob * parts;
-        const dim3 grid(items < 256 ? items : 256);
-        const size_t lds = 2 * SEQL_BUF + SEQL_ROWS * 4;
-        SEQL_DISPATCH(seql_fwd, lds, a, nprob, parts);
-        return lav_check_launch("lav_attention_fwd(long sequence)");
+// one planned launch (attn_plan: grid, block, LDS bytes, parts) of the kernel's <CAUSAL, DROP> instantiation
+template <bool CAUSAL, bool DROP>
+static void seq_launch_as(hipStream_t s, const AttnArgs& a, const AttnLaunch& l, float* delta) {
+    const int nprob = a.d.n_seq * a.d.heads;
+    switch (l.kern) {
+    case AK_SEQ_FWD3: attn_launch(seq_fwd3<CAUSAL, DROP>, l, s, a, nprob); break;
+    case AK_SEQ_DQ3: attn_launch(seq_dq3<CAUSAL, DROP>, l, s, a, nprob, delta); break;
+    case AK_SEQ_DKV3: attn_launch(seq_dkv3<CAUSAL, DROP>, l, s, a, nprob, delta); break;
+    case AK_SEQL_FWD: attn_launch(seql_fwd<CAUSAL, DROP>, l, s, a, nprob, l.split); break;
+    case AK_SEQL_DQ: attn_launch(seql_dq<CAUSAL, DROP>, l, s, a, nprob, l.split, delta); break;
+    default: attn_launch(seql_dkv<CAUSAL, DROP>, l, s, a, nprob, l.split, delta); break;
     }
-    const dim3 grid(nprob < 512 ? nprob : 512);
-    const size_t lds = 2 * SEQ3_IMG + SEQ3_ROWS * 4;
-    SEQ3_DISPATCH(seq_fwd3, lds, a, nprob);
-    return lav_check_launch("lav_attention_fwd(sequence)");
 }
-
-int seq3_bwd(void* stream, const AttnArgs& a, int problems, float* delta) {
-    hipStream_t s = (hipStream_t)stream;
-    const int nprob = problems * a.d.heads;
-    if (a.N > SEQ3_ROWS) {
-        const int parts = (a.nqt + 7) / 8, items = nprob * parts;
-        const dim3 grid(items < 256 ? items : 256);
-        const size_t lds1 = 2 * SEQL_BUF + SEQL_ROWS * 4, lds2 = 2 * SEQL_BUF + SEQL_ROWS * 8;
-        SEQL_DISPATCH(seql_dq, lds1, a, nprob, parts, delta);
-        SEQL_DISPATCH(seql_dkv, lds2, a, nprob, parts, (const float*)delta);
-        return lav_check_launch("lav_attention_bwd(long sequence)");
-    }
-    const dim3 grid(nprob < 512 ? nprob : 512);
-    const size_t lds1 = 2 * SEQ3_IMG + SEQ3_ROWS * 4, lds2 = 2 * SEQ3_IMG + SEQ3_ROWS * 8;
-    SEQ3_DISPATCH(seq_dq3, lds1, a, nprob, delta);
-    SEQ3_DISPATCH(seq_dkv3, lds2, a, nprob, (const float*)delta);
-    return lav_check_launch("lav_attention_bwd(sequence)");
+void seq_launch(hipStream_t s, const AttnArgs& a, const AttnPlan&, const AttnLaunch& l, float* delta) {
+    const bool causal = a.d.causal_from > 0, drop = a.d.dropout_p > 0.f;
+    if (causal) { if (drop) seq_launch_as<true, true>(s, a, l, delta); else seq_launch_as<true, false>(s, a, l, delta); }
+    else { if (drop) seq_launch_as<false, true>(s, a, l, delta); else seq_launch_as<false, false>(s, a, l, delta); }
 }

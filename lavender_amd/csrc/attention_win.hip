@@ -1,7 +1,7 @@
-// Persistent shifted-window attention for gfx950 (window volume N <= 256, head_dim 32): the Swin hot loop, round-3 kernels.
+// Persistent shifted-window attention for gfx950 (window volume N <= 256, head_dim 32): the Swin hot loop.
 //
 // One 512-thread workgroup (8 waves, two per SIMD) per CU owns a fixed (head, window position) pair and walks a slice of the
-// batch; wave w owns the 32-row strip w of the 256-slot window (queries in the forward / dQ pass, keys in the dK / dV pass).
+// batch; wave w owns the 32-row strip w of the 256-slot window (queries in the forward, keys in the backward).
 //
 // What round 2's counters called "waves parked 38-55 %" was one design flaw: ordinary global loads (the bias fragments of every
 // tile, the next sample's q / dO / O rows) were consumed INSIDE the tile loop while the LDS-DMA prefetch of the next sample was in
@@ -19,7 +19,7 @@
 //   3. The row sum of P (forward) is one more MFMA against a one-row "ones" fragment; delta[q] enters dP through the C operand
 //      of its MFMA (dP - delta costs nothing); padded queries are masked through lse = +inf.  VALU per score element:
 //      forward fma + exp + 1/2 max3 + 1/2 cvt_pk, backward fma + exp + mul + cvt_pk.
-//   4. K (and Q / dO in the dK / dV pass) has ONE LDS image: the XOR of the 16-byte slot is constant over the four rows a
+//   4. K (and Q / dO in the backward) has ONE LDS image: the XOR of the 16-byte slot is constant over the four rows a
 //      ds_read_b64_tr_b16 lane group gathers, so the transposing reads and the ds_read_b128 fragment reads share it.
 //   5. The relative-position-bias gradient (sum over windows and batch of dS per offset class: 128 resident accumulators per
 //      wave, the reason the round-2 dQ kernel ran one wave per SIMD with 100 spilled registers) is its own kernel, win_dbias3: a
@@ -27,7 +27,6 @@
 //      issues it on the weight-gradient stream, off the dy -> dx chain (lav_attention_bwd_bias).
 // Scores use the exp2 domain; lse is log2(sum_k 2^v).
 #include "attn_common.h"
-#include <stdlib.h>
 
 #define LOG2E 1.4426950408889634f
 #define HD 32
@@ -296,305 +295,6 @@ __global__ __launch_bounds__(512) void win_fwd3(AttnArgs a, int bsplit) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// backward pass 1: dQ, and delta[q] = sum_d dO[q,d] O[q,d] (stored NEGATED: it is the C operand of the dP MFMAs of all three
-// backward kernels).  LDS: [2][K 16 KB | V 16 KB | lse 1 KB] + wave-private strips [8][Q 2 KB | dO 2 KB | O 2 KB] + token rows.
-// The strips are single-buffered: a wave copies its strip into registers at the top of a sample and only then issues the DMA
-// of the next sample's strip into the same place.
-// ------------------------------------------------------------------------------------------------------
-template <int NT>
-__global__ __launch_bounds__(512) void win_dq3(AttnArgs a, int bsplit, float* ndelta_out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    WinGeo g;
-    if (!win_geo(a, bsplit, blockIdx.x, g)) return;
-    constexpr int BUF = 16384 * 2 + 1024;
-    char* strips = smem + 2 * BUF;
-    int* srel_l = (int*)(strips + 8 * 6144);
-    const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, hi = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int C = a.C, ld = 3 * C;
-    const float sc = a.d.scale * LOG2E;
-    if (tid < 256) { const int rel = a.d.tok_table[g.ws * 256 + tid]; srel_l[tid] = rel < 0 ? 0 : rel; }
-    const int q = wave * 32 + j;
-    const int qrel = a.d.tok_table[g.ws * 256 + q];
-    const bool q_ok = qrel >= 0;
-    const bf16_t* comb = (const bf16_t*)a.d.comb + ((long)(g.type * a.d.heads + g.head) * 64 + wave * 8) * 1024 + lane * 8;
-    Frag cb[NT][2];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) { cb[t][0].u = *(const uint4*)(comb + t * 1024); cb[t][1].u = *(const uint4*)(comb + t * 1024 + 512); }
-    const bf16x8 id0 = ident_frag(0, j, hi), id1 = ident_frag(1, j, hi);
-    __syncthreads();
-    unsigned offk[2], offq[2], offg[2];                       // a 256-row image = 16 one-KB pieces: two per wave and operand
-    const QkvAddr qa = qkv_addr(a, g.head);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        offq[i] = dma_off(srel_l, wave * 2 + i, lane, qa);
-        offk[i] = offq[i] + qa.pl_b;
-        offg[i] = dma_off(srel_l, wave * 2 + i, lane, C, g.head * HD);
-    }
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-    const unsigned strip0 = lds0 + 2 * BUF + wave * 6144;
-    const long lse_row = (long)g.ws * a.d.heads + g.head;       // + b * nWs * heads
-    auto issue_kv = [&](int b, int buf) {
-        const bf16_t* base = a.qkv + (long)b * a.tps * qa.rs;
-        const unsigned d0 = lds0 + buf * BUF + wave * 2048;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            dma16(d0 + i * 1024, base, offk[i]);
-            dma16(d0 + 16384 + i * 1024, base, offk[i] + qa.pl_b);
-        }
-        if (wave == 0)
-            dma16(lds0 + buf * BUF + 32768, a.lse + ((long)b * a.nWs * a.d.heads + lse_row) * a.Npad, (unsigned)(min(lane * 4, a.Npad - 4) * 4));
-    };
-    auto issue_strip = [&](int b) {
-        const bf16_t* bq = a.qkv + (long)b * a.tps * qa.rs;
-        const bf16_t* bg = a.dout + (long)b * a.tps * C;
-        const bf16_t* bo = a.out + (long)b * a.tps * C;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            dma16(strip0 + i * 1024, bq, offq[i]);
-            dma16(strip0 + 2048 + i * 1024, bg, offg[i]);
-            dma16(strip0 + 4096 + i * 1024, bo, offg[i]);
-        }
-    };
-    issue_kv(g.b0, 0);
-    issue_strip(g.b0);
-    dma_wait_all();
-    __syncthreads();
-
-    for (int b = g.b0; b < g.b1; ++b) {
-        const int cur = (b - g.b0) & 1;
-        const char* Ks = smem + cur * BUF;
-        const char* Vs = Ks + 16384;
-        const float* lse_l = (const float*)(Ks + 32768);
-        const char* Sq = strips + wave * 6144;
-        bf16x8 qf[2], dof[2];
-        float dl = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int off = krow_off<HD>(j, ks * 2 + hi);
-            Frag fq, fg, fo;
-            fq.u = *(const uint4*)(Sq + off); fg.u = *(const uint4*)(Sq + 2048 + off); fo.u = *(const uint4*)(Sq + 4096 + off);
-            qf[ks] = fq.b; dof[ks] = fg.b;
-            float gf[8], of[8];
-            unpack8(fg.u, gf); unpack8(fo.u, of);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dl = fmaf(gf[e], of[e], dl);
-        }
-        dl = xhalf_sum(dl);
-        const float nl = q_ok ? -lse_l[q] : -INFINITY;     // padded query: P = exp2(-inf) = 0
-        if (q_ok && hi == 0) ndelta_out[((long)b * a.nWs * a.d.heads + lse_row) * a.Npad + q] = -dl;
-        f32x16 ndl;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ndl[r] = -dl;
-        lds_wait_all();                                      // the strip is in registers: its LDS image may be overwritten
-        if (b + 1 < g.b1) { issue_kv(b + 1, cur ^ 1); issue_strip(b + 1); }
-
-        f32x16 dq = ZERO16;
-        f32x16 sa, sb, pa, pb;
-        auto front = [&](int t, f32x16& s, f32x16& dp) {    // S^T tile (+ bias) and dP^T - delta of key tile t
-            const f32x16 z = ZERO16;
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cb[t][0].b, id0, z, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cb[t][1].b, id1, s, 0, 0, 0);
-            dp = ndl;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int off = krow_off<HD>(t * 32 + j, ks * 2 + hi);
-                bf16x8 kf = *(const bf16x8*)(Ks + off);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s, 0, 0, 0);
-                bf16x8 vf = *(const bf16x8*)(Vs + off);
-                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[ks], dp, 0, 0, 0);
-            }
-        };
-        auto back = [&](int t, const f32x16& s, const f32x16& dp) {
-            uint32_t dk[8];
-#pragma unroll
-            for (int r = 0; r < 16; r += 2)
-                { const lav_f2 e = fma2(s[r], s[r + 1], sc, nl, nl); const lav_f2 d = mul2(fast_exp2(e.x), fast_exp2(e.y), dp[r], dp[r + 1]); dk[r >> 1] = pack2(d.x, d.y); }
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl) {
-                Frag df; df.u = make_uint4(dk[4 * sl], dk[4 * sl + 1], dk[4 * sl + 2], dk[4 * sl + 3]);
-                bf16x8 ktf = tr_frag_k32(Ks, t * 32 + 16 * sl, lane);
-                dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktf, df.b, dq, 0, 0, 0);
-            }
-        };
-        front(0, sa, pa);
-#pragma unroll
-        for (int t = 0; t < NT; t += 2) {
-            if (t + 1 < NT) front(t + 1, sb, pb);
-            back(t, sa, pa);
-            if (t + 1 < NT) {
-                if (t + 2 < NT) front(t + 2, sa, pa);
-                back(t + 1, sb, pb);
-            }
-        }
-        if (q_ok) {
-            bf16_t* op = a.dqkv + ((long)b * a.tps + qrel) * ld + g.head * HD;
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                uint2 w;
-                w.x = pack2(dq[r4 * 4 + 0] * a.d.scale, dq[r4 * 4 + 1] * a.d.scale);
-                w.y = pack2(dq[r4 * 4 + 2] * a.d.scale, dq[r4 * 4 + 3] * a.d.scale);
-                *(uint2*)(op + 8 * r4 + 4 * hi) = w;
-            }
-        }
-        dma_wait_all();
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// backward pass 2: dK, dV.  Wave owns key tile `wave`.  LDS: [2][Q 16 KB | dO 16 KB | lse 1 KB | -delta 1 KB] + wave-private
-// strips [8][K 2 KB | V 2 KB] + token rows.  Score tiles are queries x keys here, so lse and delta vary along the registers of
-// a lane: both come from LDS per tile (delta as the C operand of the dP MFMAs, -lse as the addend of the exponent fma).
-// ------------------------------------------------------------------------------------------------------
-template <int NT>
-__global__ __launch_bounds__(512) void win_dkv3(AttnArgs a, int bsplit, const float* ndelta_in) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    WinGeo g;
-    if (!win_geo(a, bsplit, blockIdx.x, g)) return;
-    constexpr int BUF = 16384 * 2 + 2048;
-    char* strips = smem + 2 * BUF;
-    int* srel_l = (int*)(strips + 8 * 4096);
-    const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, hi = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = a.N, C = a.C, ld = 3 * C;
-    const float sc = a.d.scale * LOG2E;
-    if (tid < 256) { const int rel = a.d.tok_table[g.ws * 256 + tid]; srel_l[tid] = rel < 0 ? 0 : rel; }
-    const int key = wave * 32 + j;
-    const int krel = a.d.tok_table[g.ws * 256 + key];
-    const bool k_ok = krel >= 0;
-    const bool wave_on = wave < NT;                         // wave-uniform: key tiles past N carry no keys
-    const bf16_t* combT = (const bf16_t*)a.d.combT + ((long)(g.type * a.d.heads + g.head) * 64 + wave * 8) * 1024 + lane * 8;
-    Frag cb[NT][2];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) { cb[t][0].u = *(const uint4*)(combT + t * 1024); cb[t][1].u = *(const uint4*)(combT + t * 1024 + 512); }
-    const bf16x8 id0 = ident_frag(0, j, hi), id1 = ident_frag(1, j, hi);
-    __syncthreads();
-    unsigned offq[2], offg[2], offk[2];
-    const QkvAddr qa = qkv_addr(a, g.head);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        offq[i] = dma_off(srel_l, wave * 2 + i, lane, qa);
-        offg[i] = dma_off(srel_l, wave * 2 + i, lane, C, g.head * HD);
-        offk[i] = offq[i] + qa.pl_b;
-    }
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-    const unsigned strip0 = lds0 + 2 * BUF + wave * 4096;
-    const long lse_row = (long)g.ws * a.d.heads + g.head;
-    auto issue_q = [&](int b, int buf) {
-        const bf16_t* bq = a.qkv + (long)b * a.tps * qa.rs;
-        const bf16_t* bg = a.dout + (long)b * a.tps * C;
-        const unsigned d0 = lds0 + buf * BUF + wave * 2048;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            dma16(d0 + i * 1024, bq, offq[i]);
-            dma16(d0 + 16384 + i * 1024, bg, offg[i]);
-        }
-        const long lo = ((long)b * a.nWs * a.d.heads + lse_row) * a.Npad;
-        if (wave == 0) dma16(lds0 + buf * BUF + 32768, a.lse + lo, (unsigned)(min(lane * 4, a.Npad - 4) * 4));
-        if (wave == 1) dma16(lds0 + buf * BUF + 32768 + 1024, ndelta_in + lo, (unsigned)(min(lane * 4, a.Npad - 4) * 4));
-    };
-    auto issue_strip = [&](int b) {
-        const bf16_t* bq = a.qkv + (long)b * a.tps * qa.rs;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            dma16(strip0 + i * 1024, bq, offk[i]);
-            dma16(strip0 + 2048 + i * 1024, bq, offk[i] + qa.pl_b);
-        }
-    };
-    issue_q(g.b0, 0);
-    issue_strip(g.b0);
-    dma_wait_all();
-    __syncthreads();
-
-    for (int b = g.b0; b < g.b1; ++b) {
-        const int cur = (b - g.b0) & 1;
-        const char* Qs = smem + cur * BUF;
-        const char* Gs = Qs + 16384;
-        const float* lse_l = (const float*)(Qs + 32768);
-        const float* ndl_l = lse_l + 256;
-        const char* Sk = strips + wave * 4096;
-        bf16x8 kf[2], vf[2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int off = krow_off<HD>(j, ks * 2 + hi);
-            kf[ks] = *(const bf16x8*)(Sk + off); vf[ks] = *(const bf16x8*)(Sk + 2048 + off);
-        }
-        lds_wait_all();
-        if (b + 1 < g.b1) { issue_q(b + 1, cur ^ 1); issue_strip(b + 1); }
-
-        if (wave_on) {
-            f32x16 dk = ZERO16, dv = ZERO16;
-#pragma unroll
-            for (int qt = 0; qt < NT; ++qt) {
-                const int q0 = qt * 32;
-                const f32x16 z = ZERO16;
-                f32x16 s, dp, nls;
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cb[qt][0].b, id0, z, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cb[qt][1].b, id1, s, 0, 0, 0);
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const int qb = q0 + 8 * r4 + 4 * hi;     // rows tile_row(4 r4 .. 4 r4 + 3, hi) are four consecutive queries
-                    const float4 d4 = *(const float4*)(ndl_l + qb);
-                    const float4 l4 = *(const float4*)(lse_l + qb);
-                    dp[4 * r4] = d4.x; dp[4 * r4 + 1] = d4.y; dp[4 * r4 + 2] = d4.z; dp[4 * r4 + 3] = d4.w;
-                    nls[4 * r4] = l4.x; nls[4 * r4 + 1] = l4.y; nls[4 * r4 + 2] = l4.z; nls[4 * r4 + 3] = l4.w;
-                }
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const int off = krow_off<HD>(q0 + j, ks * 2 + hi);
-                    bf16x8 qa = *(const bf16x8*)(Qs + off);
-                    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], s, 0, 0, 0);
-                    bf16x8 ga = *(const bf16x8*)(Gs + off);
-                    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga, vf[ks], dp, 0, 0, 0);
-                }
-                uint32_t pk[8], dsk[8];
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const lav_f2 e2 = fma2(s[r], s[r + 1], sc, -nls[r], -nls[r + 1]);
-                    float p0 = fast_exp2(e2.x), p1 = fast_exp2(e2.y);
-                    const lav_f2 dd = mul2(p0, p1, dp[r], dp[r + 1]);
-                    float d0 = dd.x, d1 = dd.y;
-                    if (qt == NT - 1) {                      // padded query rows of the last tile: their lse / delta slots were never
-                        const int qq = q0 + tile_row(r, hi);     // written (selects, not multiplies: the garbage may be inf / NaN)
-                        if (qq >= N) { p0 = 0.f; d0 = 0.f; }
-                        if (qq + 1 >= N) { p1 = 0.f; d1 = 0.f; }
-                    }
-                    pk[r >> 1] = pack2(p0, p1);
-                    dsk[r >> 1] = pack2(d0, d1);
-                }
-#pragma unroll
-                for (int sl = 0; sl < 2; ++sl) {
-                    Frag pf, df;
-                    pf.u = make_uint4(pk[4 * sl], pk[4 * sl + 1], pk[4 * sl + 2], pk[4 * sl + 3]);
-                    df.u = make_uint4(dsk[4 * sl], dsk[4 * sl + 1], dsk[4 * sl + 2], dsk[4 * sl + 3]);
-                    bf16x8 gt = tr_frag_k32(Gs, q0 + 16 * sl, lane);
-                    dv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gt, pf.b, dv, 0, 0, 0);
-                    bf16x8 qt_ = tr_frag_k32(Qs, q0 + 16 * sl, lane);
-                    dk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt_, df.b, dk, 0, 0, 0);
-                }
-            }
-            if (k_ok) {
-                bf16_t* op = a.dqkv + ((long)b * a.tps + krel) * ld + g.head * HD;
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const int d = 8 * r4 + 4 * hi;
-                    uint2 w;
-                    w.x = pack2(dk[r4 * 4 + 0] * a.d.scale, dk[r4 * 4 + 1] * a.d.scale);
-                    w.y = pack2(dk[r4 * 4 + 2] * a.d.scale, dk[r4 * 4 + 3] * a.d.scale);
-                    *(uint2*)(op + C + d) = w;
-                    w.x = pack2(dv[r4 * 4 + 0], dv[r4 * 4 + 1]);
-                    w.y = pack2(dv[r4 * 4 + 2], dv[r4 * 4 + 3]);
-                    *(uint2*)(op + 2 * C + d) = w;
-                }
-            }
-        }
-        dma_wait_all();
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
 // backward, ONE pass (round 5): dQ, dK, dV of a (window, head) from a single evaluation of S and dP.
 //
 // Wave w owns key tile w: dK / dV accumulate in its registers over the query tiles (contraction over queries: P and dS are B
@@ -608,7 +308,7 @@ __global__ __launch_bounds__(512) void win_dkv3(AttnArgs a, int bsplit, const fl
 // that tile's LDS slot is dead, so its first 2 KB serve as the wave's dS^T scratch.
 // delta[q] = dO[q] . O[q] is computed at the top of a sample by the wave whose index is the query strip (O arrives as a
 // wave-private strip) and shared through LDS; -delta also goes to global memory for win_dbias3 (weight-gradient stream).
-// What two passes cost: S, dP, the exponentials and both packs twice (18 MFMAs + 2 x 16 exp per tile pair, now 12 + 16), q / k / v / dO
+// What the two passes it replaced (dQ, then dK / dV: profiles/r05_win_bwd1.md) cost: S, dP, the exponentials and both packs twice (18 MFMAs + 2 x 16 exp per tile pair, now 12 + 16), q / k / v / dO
 // fetched twice, lse / delta round trips.  Padded query slots need no select: the forward stores lse = +inf for them.
 // LDS: [2][Q 16 KB | dO 16 KB | lse 1 KB] + -delta 1 KB + strips [8][K 2 KB | V 2 KB | O 2 KB] + dQ tiles [8][4 KB] + token rows 1 KB
 //      = 148 KB.
@@ -1287,72 +987,27 @@ extern "C" int lav_attention_build_bias(void* stream, const lav_attn_desc* d) {
     return lav_check_launch("lav_attention_build_bias");
 }
 
-static int pick_bsplit(const AttnArgs& a, int per_pair = 1) {
-    const int base = a.d.heads * a.nWs * per_pair;
-    int bs = (256 + base - 1) / base;
-    if (bs > a.d.B) bs = a.d.B;
-    if (bs < 1) bs = 1;
-    return bs;
-}
-
-template <typename Kn>
-static void big_lds(Kn k, size_t bytes) {
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    (void)hipGetLastError();
-}
-
 #define NT_SWITCH(nt, MACRO)                                                                         \
     switch (nt) { case 8: MACRO(8) break; case 7: MACRO(7) break; case 6: MACRO(6) break; case 5: MACRO(5) break; \
                   case 4: MACRO(4) break; case 3: MACRO(3) break; case 2: MACRO(2) break; default: MACRO(1) }
 
-int win_persistent_fwd(void* stream, const AttnArgs& a) {
-    const int bs = pick_bsplit(a);
-    const size_t lds = 2 * 49152 + 1024;
-    const dim3 grid(a.d.heads * a.nWs * bs);
-#define FWD3_(NT) { big_lds(win_fwd3<NT>, lds); hipLaunchKernelGGL(win_fwd3<NT>, grid, dim3(512), lds, (hipStream_t)stream, a, bs); }
-    NT_SWITCH((a.N + 31) / 32, FWD3_)
-#undef FWD3_
-    return lav_check_launch("lav_attention_fwd(window, persistent)");
-}
-
-// needs lse (forward) and -delta (written by the dQ pass of win_persistent_bwd on the same problem)
-int win_persistent_dbias(void* stream, const AttnArgs& a, const float* ndelta) {
-    const int bs = pick_bsplit(a, 2);
-    const dim3 grid(a.d.heads * a.nWs * bs * 2);
-    const size_t lds = 128 * 257 * 4 + 1024;                 // max(two operand buffers, the flush matrix) + token rows
-#define DB3_(NT) { big_lds(win_dbias3<NT>, lds); hipLaunchKernelGGL(win_dbias3<NT>, grid, dim3(512), lds, (hipStream_t)stream, a, bs, ndelta); }
-    NT_SWITCH((a.N + 31) / 32, DB3_)
-#undef DB3_
-    return lav_check_launch("lav_attention_bwd_bias(window, persistent)");
-}
-
 static unsigned long long* g_win_prof = nullptr;            // probe hook (tools/win_prof.py): device buffer for the stamped build of win_bwd1<8>
 extern "C" void lav_probe_win_prof(void* buf) { g_win_prof = (unsigned long long*)buf; }
-int win_persistent_bwd(void* stream, const AttnArgs& a, float* ndelta) {
-    const int bs = pick_bsplit(a);
-    const dim3 grid(a.d.heads * a.nWs * bs);
-    static const bool one_pass = getenv("LAV_WIN_BWD1") ? atoi(getenv("LAV_WIN_BWD1")) != 0 : true;   // probe hook: 0 = the two-pass kernels of round 3
-    if (one_pass) {
-        const size_t lds = 2 * (32768 + 1024) + 1024 + 8 * 6144 + 8 * 4096 + 1024 + 64;
-        if (g_win_prof && (a.N + 31) / 32 == 8) {
-            big_lds(win_bwd1<8, true>, lds);
-            hipLaunchKernelGGL((win_bwd1<8, true>), grid, dim3(512), lds, (hipStream_t)stream, a, bs, ndelta, g_win_prof);
-            return lav_check_launch("lav_attention_bwd(window, one pass, stamped)");
-        }
-#define BWD1_(NT) { big_lds(win_bwd1<NT>, lds); hipLaunchKernelGGL(win_bwd1<NT>, grid, dim3(512), lds, (hipStream_t)stream, a, bs, ndelta, (unsigned long long*)nullptr); }
-        NT_SWITCH((a.N + 31) / 32, BWD1_)
-#undef BWD1_
-        if (a.dbias) return win_persistent_dbias(stream, a, ndelta);
-        return lav_check_launch("lav_attention_bwd(window, one pass)");
+
+// one planned launch (attn_plan: grid, LDS bytes, bsplit, NT).  ndelta: win_bwd1 writes -delta there, win_dbias3 reads it (with the forward's lse)
+void win_launch(hipStream_t s, const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, float* ndelta) {
+#define FWD3_(NT) attn_launch(win_fwd3<NT>, l, s, a, l.split);
+#define BWD1_(NT) attn_launch(win_bwd1<NT>, l, s, a, l.split, ndelta, nullptr);
+#define DB3_(NT) attn_launch(win_dbias3<NT>, l, s, a, l.split, ndelta);
+    switch (l.kern) {
+    case AK_WIN_FWD3: NT_SWITCH(p.NT, FWD3_) break;
+    case AK_WIN_BWD1:
+        if (g_win_prof && p.NT == 8) attn_launch(win_bwd1<8, true>, l, s, a, l.split, ndelta, g_win_prof);
+        else NT_SWITCH(p.NT, BWD1_)
+        break;
+    default: NT_SWITCH(p.NT, DB3_) break;
     }
-    const size_t lds1 = 2 * (32768 + 1024) + 8 * 6144 + 1024;
-    const size_t lds2 = 2 * (32768 + 2048) + 8 * 4096 + 1024;
-#define DQ3_(NT) { big_lds(win_dq3<NT>, lds1); hipLaunchKernelGGL(win_dq3<NT>, grid, dim3(512), lds1, (hipStream_t)stream, a, bs, ndelta); }
-    NT_SWITCH((a.N + 31) / 32, DQ3_)
-#undef DQ3_
-#define DKV3_(NT) { big_lds(win_dkv3<NT>, lds2); hipLaunchKernelGGL(win_dkv3<NT>, grid, dim3(512), lds2, (hipStream_t)stream, a, bs, (const float*)ndelta); }
-    NT_SWITCH((a.N + 31) / 32, DKV3_)
-#undef DKV3_
-    if (a.dbias) return win_persistent_dbias(stream, a, ndelta);
-    return lav_check_launch("lav_attention_bwd(window, persistent)");
+#undef FWD3_
+#undef BWD1_
+#undef DB3_
 }

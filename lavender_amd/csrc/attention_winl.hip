@@ -22,12 +22,9 @@
 //     per-offset-class box sums, one global atomic per class.
 // Scores use the exp2 domain; lse is log2(sum_k 2^v), stored [window * heads + head][Npad]; delta follows it (backward scratch).
 #include "attn_common.h"
-#include <stdlib.h>
 
 #define LOG2E 1.4426950408889634f
 #define HD 32
-#define WL_ROWS 768
-#define WL_IMG (WL_ROWS * 64)
 
 __device__ __forceinline__ void wl_dma16(unsigned lds_dst, const void* sbase, unsigned voff) {
     unsigned keep_m0;
@@ -56,7 +53,6 @@ __device__ __forceinline__ float wmax3(float a, float b, float c) { return fmaxf
 
 // A workgroup keeps ONE head for its whole walk (table column loaded once, bias gradient flushed once): workgroup b serves head
 // b % heads and takes that head's (window, query part) items bi, bi + Gh, ... where Gh = workgroups of the head.
-struct WlTab { int lo, n, mc; };     // first reachable table row, reachable rows, code of the last window slot
 struct WlWalk { int head, first, step, count; };
 __device__ __forceinline__ WlWalk wl_walk(const AttnArgs& a, int nwin, int QS) {
     WlWalk w;
@@ -508,10 +504,6 @@ __global__ __launch_bounds__(512) void winl_dkv(AttnArgs a, int nwin, int QS, Wl
 // LDS: max([2][K 16 KB | V 16 KB | Q 8 KB | dO 8 KB | lse 1 KB | delta 1 KB | rowsK | rowsQ | krK | krQ], flush matrix
 // 128 x 257 floats) | kcnK | kcnQ | table column.
 // ------------------------------------------------------------------------------------------------------
-#define WLB_BUF (16384 * 2 + 8192 * 2 + 2048 + 384 * 4 * 2)
-#define WLB_DLD 257
-#define WLB_MAIN (2 * WLB_BUF > 128 * WLB_DLD * 4 ? 2 * WLB_BUF : 128 * WLB_DLD * 4)
-
 __global__ __launch_bounds__(512) void winl_dbias(AttnArgs a, int nwin, int WS, WlTab tb, const float* delta_in) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int* kcnK = (int*)(smem + WLB_MAIN);
@@ -693,75 +685,13 @@ __global__ __launch_bounds__(512) void winl_dbias(AttnArgs a, int nwin, int WS, 
 }
 
 // ------------------------------------------------------------------------------------------------------
-template <typename Kn>
-static void wl_lds(Kn k, size_t bytes) {
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    (void)hipGetLastError();
-}
-
-static const bool lav_winl_on = getenv("LAV_WINL") ? atoi(getenv("LAV_WINL")) != 0 : true;   // probe hook: 0 = generic kernels
-
-static int lav_winl_parts = 0;                             // test hook: force the number of query parts per problem (0 = by problem count)
-extern "C" int lav_winl_select(int parts) { const int old = lav_winl_parts; lav_winl_parts = parts; return old; }
-
-static WlTab wl_tab(const AttnArgs& a) {
-    const lav_attn_desc& d = a.d;
-    const int i = a.N - 1;                                   // codes grow with the slot index: the last slot has the largest
-    WlTab t;
-    t.mc = (i / (d.cfg_wh * d.cfg_ww)) * a.cstride_d + ((i / d.cfg_ww) % d.cfg_wh) * a.cstride_h + (i % d.cfg_ww);
-    t.lo = a.tbl_const - t.mc;
-    t.n = 2 * t.mc + 1;
-    return t;
-}
-
-bool winl_supported(const AttnArgs& a) {
-    if (lav_winl_parts < 0) return false;                     // test hook: lav_winl_select(-1) routes large windows to the generic kernels
-    if (!(lav_winl_on && a.d.mode == 0 && !a.d.comb && a.N <= WL_ROWS)) return false;
-    const double qkv_bytes = (double)a.d.B * a.tps * 3.0 * a.C * 2.0;             // DMA offsets are 32-bit
-    const WlTab t = wl_tab(a);
-    return qkv_bytes < 4.0e9 && t.lo >= 0 && t.lo + t.n <= a.tbl_rows && (size_t)t.n * 4 + 2 * WL_IMG + 5 * WL_ROWS * 4 + 512 <= 160 * 1024 &&
-           (size_t)t.n * 4 + WLB_MAIN + 384 * 4 + 512 <= 160 * 1024;
-}
-
-static int wl_parts(int problems) { return lav_winl_parts > 0 ? lav_winl_parts : problems >= 1024 ? 1 : 3; }
-
-int winl_fwd_launch(void* stream, const AttnArgs& a, int nwin) {
-    hipStream_t s = (hipStream_t)stream;
-    const WlTab tb = wl_tab(a);
-    const int QS = wl_parts(nwin * a.d.heads), items = nwin * a.d.heads * QS;
-    const size_t lds = 2 * WL_IMG + 3 * WL_ROWS * 4 + (size_t)tb.n * 4;
-    wl_lds(winl_fwd, lds);
-    hipLaunchKernelGGL(winl_fwd, dim3(items < 256 ? items : 256), dim3(512), lds, s, a, nwin, QS, tb);
-    return lav_check_launch("lav_attention_fwd(large window)");
-}
-
-int winl_dbias_launch(void* stream, const AttnArgs& a, int nwin, const float* delta);
-
-int winl_bwd_launch(void* stream, const AttnArgs& a, int nwin, float* delta) {
-    hipStream_t s = (hipStream_t)stream;
-    const WlTab tb = wl_tab(a);
-    const int QS = wl_parts(nwin * a.d.heads), items = nwin * a.d.heads * QS;
-    const dim3 grid(items < 256 ? items : 256);
-    const size_t lds1 = 2 * WL_IMG + 3 * WL_ROWS * 4 + (size_t)tb.n * 4;
-    const size_t lds2 = 2 * WL_IMG + 5 * WL_ROWS * 4 + (size_t)tb.n * 4;
-    wl_lds(winl_dq, lds1);
-    hipLaunchKernelGGL(winl_dq, grid, dim3(512), lds1, s, a, nwin, QS, tb, delta);
-    wl_lds(winl_dkv, lds2);
-    hipLaunchKernelGGL(winl_dkv, grid, dim3(512), lds2, s, a, nwin, QS, tb, (const float*)delta);
-    if (a.dbias) return winl_dbias_launch(stream, a, nwin, delta);
-    return lav_check_launch("lav_attention_bwd(large window)");
-}
-
-// needs lse (forward) and delta (written by winl_dq on the same problems)
-int winl_dbias_launch(void* stream, const AttnArgs& a, int nwin, const float* delta) {
-    const WlTab tb = wl_tab(a);
-    const int nqb = (a.nqt + 3) / 4, nkb = (a.nqt + 7) / 8;
-    const int base = a.d.heads * nqb * nkb;
-    int WS = (512 + base - 1) / base;
-    if (WS > nwin) WS = nwin;
-    if (WS < 1) WS = 1;
-    const size_t lds = WLB_MAIN + 384 * 4 + (size_t)tb.n * 4;
-    wl_lds(winl_dbias, lds);
-    hipLaunchKernelGGL(winl_dbias, dim3(base * WS), dim3(512), lds, (hipStream_t)stream, a, nwin, WS, tb, delta);
-    return lav_check_launch("lav_attention_bwd_bias(large window)");
+// one planned launch (attn_plan: grid, LDS bytes, query parts / window slices, the reachable table rows)
+void winl_launch(hipStream_t s, const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, float* delta) {
+    const int nwin = a.d.B * a.nWs;
+    switch (l.kern) {
+    case AK_WINL_FWD: attn_launch(winl_fwd, l, s, a, nwin, l.split, p.tab); break;
+    case AK_WINL_DQ: attn_launch(winl_dq, l, s, a, nwin, l.split, p.tab, delta); break;
+    case AK_WINL_DKV: attn_launch(winl_dkv, l, s, a, nwin, l.split, p.tab, delta); break;
+    default: attn_launch(winl_dbias, l, s, a, nwin, l.split, p.tab, delta); break;      // needs lse (forward) and delta (winl_dq on the same problems)
+    }
 }

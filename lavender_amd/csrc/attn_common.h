@@ -26,29 +26,62 @@ struct AttnArgs {
 };
 
 int attn_setup(const lav_attn_desc* d, AttnArgs& a, int& problems);
-int win_persistent_fwd(void* stream, const AttnArgs& a);
-int win_persistent_bwd(void* stream, const AttnArgs& a, float* ndelta);     // dQ, dK, dV (+ bias gradient when a.dbias)
-int win_persistent_dbias(void* stream, const AttnArgs& a, const float* ndelta);
-// window mode without the precomputed tables, N <= 768 (attention_winl.hip)
-bool winl_supported(const AttnArgs& a);
-int winl_fwd_launch(void* stream, const AttnArgs& a, int nwin);
-int winl_bwd_launch(void* stream, const AttnArgs& a, int nwin, float* delta);     // dQ, dK, dV (+ bias gradient when a.dbias)
-int winl_dbias_launch(void* stream, const AttnArgs& a, int nwin, const float* delta);
-// sequence mode, L <= 288 (attention_seq.hip)
-bool seq3_supported(const AttnArgs& a);
-int seq3_fwd(void* stream, const AttnArgs& a, int problems);
-int seq3_bwd(void* stream, const AttnArgs& a, int problems, float* delta);
 
-// fast window path: token rows from the precomputed per-window table instead of div/mod chains
-__device__ __forceinline__ int tok_row(const AttnArgs& a, int win, int i) {
-    const int ws = win % a.nWs, b = win / a.nWs;
-    return a.d.tok_table[ws * 256 + i] + b * a.tps;
-}
-// fragment-ordered bias+mask tile: 16 consecutive bf16 per lane (two 16-byte loads)
-__device__ __forceinline__ void comb_tile(const bf16_t* base, int tile, int lane, float* c) {
-    const uint4* p = (const uint4*)(base + ((long)tile * 64 + lane) * 16);
-    uint4 u0 = p[0], u1 = p[1];
-    unpack8(u0, c); unpack8(u1, c + 8);
+// ---- route plan (attention.hip: attn_plan) -------------------------------------------------------------------------------------
+// LDS geometry of the specialised kernels: the plan sizes their launches with it, the kernels lay their LDS out with it.
+#define WL_ROWS 768                                        // large windows (attention_winl.hip): rows of an operand image
+#define WL_IMG (WL_ROWS * 64)
+#define WLB_BUF (16384 * 2 + 8192 * 2 + 2048 + 384 * 4 * 2)
+#define WLB_DLD 257
+#define WLB_MAIN (2 * WLB_BUF > 128 * WLB_DLD * 4 ? 2 * WLB_BUF : 128 * WLB_DLD * 4)
+#define SEQ3_ROWS 288                                      // one-image sequences (attention_seq.hip): LDS image rows
+#define SEQ3_IMG (SEQ3_ROWS * 128)
+#define SEQL_ROWS 768                                      // chunked sequences
+#define SEQL_CH 256                                        // rows per chunk
+#define SEQL_IMG (SEQL_CH * 128)
+#define SEQL_BUF (2 * SEQL_IMG)
+#define WIN_KL 256                                         // generic kernels (attention.hip): keys / queries staged per pass
+#define SEQ_KL_FWD 288   // forward: K/V of a whole fusion sequence (L <= 288) staged once, two blocks per CU
+#define SEQ_KL 128       // backward dQ pass: 128-key chunks -> 48 KB of LDS, the register file (not LDS) sets the occupancy
+#define SEQ_QL 128       // backward dK/dV pass: 128-query chunks (4 staged copies = 64 KB): two blocks per CU instead of one
+
+struct WlTab { int lo, n, mc; };     // large windows: first reachable bias-table row, reachable rows, code of the last window slot
+
+enum AttnRoute { AR_WIN_PERSISTENT, AR_WIN_LARGE, AR_SEQ_ONE, AR_SEQ_CHUNKED, AR_GEN_WINDOW, AR_GEN_SEQ, AR_COUNT };
+enum AttnPass { AP_FWD, AP_BWD, AP_BWD_BIAS, AP_BIAS, AP_COUNT };   // forward; dQ / dK / dV; the same + bias-table gradient; that gradient alone
+enum AttnKernelId {                                                 // family by family: a launch goes to the file that holds its kernel
+    AK_WIN_FWD3, AK_WIN_BWD1, AK_WIN_DBIAS3, AK_WINL_FWD, AK_WINL_DQ, AK_WINL_DKV, AK_WINL_DBIAS,
+    AK_SEQ_FWD3, AK_SEQ_DQ3, AK_SEQ_DKV3, AK_SEQL_FWD, AK_SEQL_DQ, AK_SEQL_DKV, AK_GEN_FWD, AK_GEN_DQ, AK_GEN_DKV, AK_COUNT
+};
+// One launch.  split = the kernel's own partition scalar: bsplit (batch slices per (head, window position): win_*), QS (query parts per problem:
+// winl_fwd / dq / dkv), WS (window slices: winl_dbias), parts (8-tile parts per problem: seql_*), R (32-row tiles per wave: generic); 0 = none.
+struct AttnLaunch { int kern; unsigned grid_x, grid_y, block; size_t lds; int split; };
+struct AttnPlan {
+    AttnRoute route;
+    int NT;                // 32-row tiles of a problem (the persistent kernels' template argument)
+    WlTab tab;             // AR_WIN_LARGE
+    bool bias_split;       // the bias-table gradient can run as its own launch (AP_BIAS is not empty)
+    bool delta_negated;    // the backward leaves -delta behind the lse (win_bwd1 writes it, win_dbias3 reads it); every other route +delta
+    int n[AP_COUNT];       // launches of each pass, in order (AP_BIAS: 0 = lav_attention_bwd has to produce the bias-table gradient)
+    AttnLaunch launch[AP_COUNT][3];
+};
+// the process switches: LAV_WINL / LAV_SEQL (0 = generic kernels for large windows / long sequences) and lav_winl_select's query parts
+struct AttnSwitches { bool winl, seql; int winl_parts; };
+AttnPlan attn_plan(const AttnArgs& a, int problems, const AttnSwitches& sw);
+
+// the families' launch functions: one planned launch of a kernel they hold (delta: the scratch behind the lse)
+void win_launch(hipStream_t s, const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, float* delta);      // attention_win.hip
+void winl_launch(hipStream_t s, const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, float* delta);     // attention_winl.hip
+void seq_launch(hipStream_t s, const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, float* delta);      // attention_seq.hip
+
+// raises the kernel's dynamic-LDS limit to the launch's bytes and launches it; the arguments convert to the kernel's parameter types
+template <typename T> struct AttnParam { typedef T type; };
+template <typename... P>
+static void attn_launch(void (*kern)(P...), const AttnLaunch& l, hipStream_t s, typename AttnParam<P>::type... args) {
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds);
+    (void)hipGetLastError();
+    void* av[] = {(void*)&args...};
+    (void)hipLaunchKernel((const void*)kern, dim3(l.grid_x, l.grid_y), dim3(l.block), av, l.lds, s);
 }
 
 __device__ __forceinline__ int tile_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
@@ -121,9 +154,6 @@ __device__ __forceinline__ bf16x8 as_bf16x8(uint4 v) {
 }
 __device__ __forceinline__ bf16x8 pack_frag(const float* p) {
     union { uint4 u; bf16x8 b; } x; x.u = pack8(p); return x.b;
-}
-__device__ __forceinline__ bf16x8 frag2(uint2 lo, uint2 hi) {
-    union { uint4 u; bf16x8 b; } x; x.u = make_uint4(lo.x, lo.y, hi.x, hi.y); return x.b;
 }
 
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;

@@ -487,6 +487,15 @@ class Attn:
     def bwd_bias(self, qkv, dout, lse, dbias):
         L.check(L.lib.lav_attention_bwd_bias(_s(), C.byref(self.d), _p(qkv), _p(dout), _p(lse), _p(dbias)), "lav_attention_bwd_bias")
 
+    def plan(self, which=0):
+        """the launches pass `which` would make (0 forward, 1 backward, 2 backward with the bias-table gradient, 3 that gradient alone) as
+        lav_attn_launch_info entries (kernel, route, grid, block, LDS bytes, split, delta_negated), without making them: lav_attention_plan"""
+        out = (L.AttnLaunchInfo * 4)()
+        n = L.lib.lav_attention_plan(C.byref(self.d), which, out, 4)
+        if n < 0:
+            L.check(n, "lav_attention_plan")
+        return list(out[:n])
+
 
 def patch_im2col(img, B, T, H, W, frame_major):
     out = torch.empty((B * T * (H // 4) * (W // 4), 96), dtype=bf16, device=img.device)

@@ -2,12 +2,13 @@
 log2-domain lse, the delta scratch behind it, dQ / dK / dV and the bias-table gradient -- plus the per-slice relative-norm check against the
 rounding model, and exact (bit-for-bit) invariants: masked keys, the seq2seq block structure, window independence and repeatability.
 
-Paths are chosen by shape (the env probes LAV_SEQL / LAV_WINL stay at their defaults): window persistent (N <= 256, asserted through the
-fragment tables), window large (257 <= N <= 768, winl_*), window generic (N > 768, or lav_winl_select(-1)), sequence one-image (L <= 288),
-chunked (289 <= L <= 768), generic (L > 768), and the decode attention with its split-K combine.
+Paths are chosen by shape (the env probes LAV_SEQL / LAV_WINL stay at their defaults) and every case asserts the route it expects against the
+library's own plan (lav_attention_plan) before it launches: window persistent (N <= 256 with the fragment tables), window large (N <= 768
+without them, winl_*, 1 or 3 query parts), window generic (N > 768, or lav_winl_select(-1)), sequence one-image (L <= 288), chunked
+(289 <= L <= 768), generic (L > 768), and the decode attention with its split-K combine.
 
-The delta scratch: lav_attention_bwd stores delta = sum_d dO O behind the lse; the persistent window kernels store it NEGATED (it is the C
-operand of their dP MFMAs, attention_win.hip:299), every other path stores +delta."""
+The delta scratch: lav_attention_bwd stores delta = sum_d dO O behind the lse; the persistent window route stores it NEGATED (win_bwd1 writes
+-delta, the C operand of its dP MFMAs, and win_dbias3 reads it), every other route stores +delta.  The sign is taken from the plan."""
 import pytest
 import torch
 
@@ -56,6 +57,26 @@ WIN_CASES = {   # B, D, H, W, heads, window, shift, configured window, qkv_headm
     "g392": (1, 16, 14, 14, 1, (8, 7, 7), (4, 3, 3), (8, 7, 7), 0, -1),
     "g800": (1, 8, 10, 20, 1, (8, 10, 10), (0, 5, 5), (8, 10, 10), 0, None),
 }
+PERSISTENT = ("window persistent", ["win_fwd3"], ["win_bwd1", "win_dbias3"])        # route, forward kernels, kernels of the backward with the bias-table gradient
+LARGE = ("window large", ["winl_fwd"], ["winl_dq", "winl_dkv", "winl_dbias"])
+GENERIC = ("generic window", ["attn_fwd_kernel"], ["attn_bwd_dq_kernel", "attn_bwd_dkv_kernel"])
+WIN_ROUTES = {   # expected route and, on the large-window route, query parts per problem (few problems: 3 unless lav_winl_select forces 1)
+    "p49": (PERSISTENT, None), "p180_clamped": (PERSISTENT, None), "p245_shift": (PERSISTENT, None), "p245_shift_hm": (PERSISTENT, None),
+    "p256": (PERSISTENT, None), "l288": (LARGE, 3), "l288_parts1": (LARGE, 1), "l392": (LARGE, 3), "l720_shift": (LARGE, 3),
+    "l720_shift_parts1": (LARGE, 1), "g392": (GENERIC, None), "g800": (GENERIC, None),
+}
+assert set(WIN_ROUTES) == set(WIN_CASES)
+
+
+def _assert_route(att, route, parts=None):
+    """the library's plan for this descriptor names the expected route and kernels; returns whether the route keeps -delta"""
+    name, fwd_kernels, bwd_kernels = route
+    fwd, bwd = att.plan(0), att.plan(2)
+    assert {l.route.decode() for l in fwd + bwd} == {name}, [l.route for l in fwd + bwd]
+    assert [l.kernel.decode() for l in fwd] == fwd_kernels and [l.kernel.decode() for l in bwd] == bwd_kernels
+    if parts is not None:
+        assert [l.split for l in fwd + bwd[:2]] == [parts] * 3
+    return bool(fwd[0].delta_negated)
 
 
 class _WinSelect:
@@ -73,9 +94,9 @@ class _WinSelect:
             _lib.lib.lav_winl_select(self.old)
 
 
-def _win_run(case, qkv, table, dout, split=False):
-    """forward + backward of one window launch; returns (att, out, lse buffer, dqkv, dtab)"""
-    B, D, H, W, heads, win, shift, cfg, hm, parts = case
+def _win_run(name, qkv, table, dout, split=False):
+    """forward + backward of one window launch on the route WIN_ROUTES expects; returns (att, out, lse buffer, dqkv, dtab)"""
+    B, D, H, W, heads, win, shift, cfg, hm, parts = WIN_CASES[name]
     M, C = B * D * H * W, heads * 32
     x = qkv.view(M, 3, heads, 32).permute(1, 2, 0, 3).contiguous().view(M, 3 * C) if hm else qkv
     att = K().Attn(0, heads, 32, B=B, D=D, H=H, W=W, wd=win[0], wh=win[1], ww=win[2], sd=shift[0], sh=shift[1], sw=shift[2],
@@ -83,6 +104,7 @@ def _win_run(case, qkv, table, dout, split=False):
     N = win[0] * win[1] * win[2]
     assert (N <= 256) == hasattr(att, "comb")
     with _WinSelect(parts):
+        att.negated = _assert_route(att, *WIN_ROUTES[name])
         buf = torch.full((att.lse_elems(),), float("nan"), device=DEV)
         out = torch.empty(M, C, dtype=bf16, device=DEV)
         att.fwd(x, out, buf)
@@ -111,16 +133,17 @@ def _win_inputs(case, seed=0):
 def test_window_attention_within_bounds(name):
     case = WIN_CASES[name]
     geo, qkv, dout, table = _win_inputs(case)
-    persistent = geo.N <= 256
+    att, *_ = _win_run(name, qkv, table, dout)
+    persistent = att.negated                          # the plan's flag: the route keeps -delta (win_bwd1 writes it, win_dbias3 reads it)
+    assert persistent == (WIN_ROUTES[name][0] is PERSISTENT)
     ref, pred = AB.win_case(geo, qkv.double(), table, dout.double(), persistent)
     launches = [False]
-    att, *_ = _win_run(case, qkv, table, dout)
     if att.split_ok:
         launches.append(True)                         # the engine's form: dQ / dK / dV, then the bias-table gradient as its own launch
     for split in launches:
-        att, out, buf, dqkv, dtab = _win_run(case, qkv, table, dout, split)
+        att, out, buf, dqkv, dtab = _win_run(name, qkv, table, dout, split)
         lse, delta = _scratch(buf, geo.Bw * geo.heads, geo.N)
-        sign = -1.0 if persistent else 1.0            # persistent window kernels keep -delta (attention_win.hip:299, 385, 727)
+        sign = -1.0 if att.negated else 1.0
         got = dict(o=geo.gather(out), lse2=lse, delta=sign * delta, dq=geo.gather(dqkv, 0), dk=geo.gather(dqkv, 1), dv=geo.gather(dqkv, 2),
                    dtab=dtab)
         fails, stats = AB.check_all(got, ref, dict(pred, dtab=pred["dtab_bf16" if att.split_ok else "dtab"]))
@@ -133,14 +156,14 @@ def test_window_attention_windows_are_independent_and_runs_repeat(name):
     two runs on the same inputs give the same O and dqkv"""
     case = WIN_CASES[name]
     geo, qkv, dout, table = _win_inputs(case, seed=3)
-    _, out0, _, dq0, _ = _win_run(case, qkv, table, dout)
-    _, out1, _, dq1, _ = _win_run(case, qkv, table, dout)
+    _, out0, _, dq0, _ = _win_run(name, qkv, table, dout)
+    _, out1, _, dq1, _ = _win_run(name, qkv, table, dout)
     assert torch.equal(out0, out1) and torch.equal(dq0, dq1), "two runs differ"
     w = min(geo.Bw - 1, geo.Bw // 2 + 1)
     rows = geo.rows[w]
     qkv2 = qkv.clone()
     qkv2[rows] = _rb((rows.numel(), qkv.shape[1]), 99)
-    _, out2, _, dq2, _ = _win_run(case, qkv2, table, dout)
+    _, out2, _, dq2, _ = _win_run(name, qkv2, table, dout)
     other = torch.ones(geo.M, dtype=torch.bool, device=DEV)
     other[rows] = False
     assert geo.Bw > 1 and bool(other.any())
@@ -151,6 +174,11 @@ def test_window_attention_windows_are_independent_and_runs_repeat(name):
 
 # ---------------------------------------------------------------------------------------------------------------------------- sequence
 SEQ_L = [50, 282, 288, 289, 300, 757, 768, 769, 800]
+SEQ_ONE = ("sequence one-image", ["seq_fwd3"], ["seq_dq3", "seq_dkv3"])
+SEQ_CHUNKED = ("sequence chunked", ["seql_fwd"], ["seql_dq", "seql_dkv"])
+SEQ_GENERIC = ("generic sequence", ["attn_fwd_kernel"], ["attn_bwd_dq_kernel", "attn_bwd_dkv_kernel"])
+SEQ_ROUTES = {50: SEQ_ONE, 282: SEQ_ONE, 288: SEQ_ONE, 289: SEQ_CHUNKED, 300: SEQ_CHUNKED, 757: SEQ_CHUNKED, 768: SEQ_CHUNKED, 769: SEQ_GENERIC,
+              800: SEQ_GENERIC}
 
 
 def _seq_inputs(n, L, heads, seed=0):
@@ -166,6 +194,7 @@ def _seq_inputs(n, L, heads, seed=0):
 def _seq_run(n, L, heads, qkv, dout, mask, cf=0, p=0.0, seed=0):
     Hd = heads * 64
     att = K().Attn(1, heads, 64, n_seq=n, L=L, key_mask=mask.to(DEV), dropout_p=p, seed=seed, causal_from=cf)
+    assert not _assert_route(att, SEQ_ROUTES[L])       # every sequence route keeps +delta
     buf = torch.full((att.lse_elems(),), float("nan"), device=DEV)
     out = torch.empty(n * L, Hd, dtype=bf16, device=DEV)
     att.fwd(qkv, out, buf)

@@ -774,6 +774,7 @@ def test_window_attention_fwd_bwd(case):
     att = K().Attn(0, heads, 32, B=B, D=D, H=H, W=W, wd=win[0], wh=win[1], ww=win[2], sd=shift[0], sh=shift[1], sw=shift[2],
                    cfg_wd=cfg[0], cfg_wh=cfg[1], cfg_ww=cfg[2], bias_table=table)
     assert (win[0] * win[1] * win[2] <= 256) == hasattr(att, "comb")
+    assert (att.plan(0)[0].route == b"window persistent") == hasattr(att, "comb")      # the tables are what selects the persistent kernels
     if len(case) > 9:
         from lavender_amd import _lib
         old_parts = _lib.lib.lav_winl_select(case[9])
