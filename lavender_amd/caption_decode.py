@@ -161,7 +161,7 @@ class KVDecoder:
 
     def __init__(self, model, feat_img, mask_img, max_len, beams=1):
         self.m = model
-        arena = model.arena()
+        model.arena()                                          # the layers' constants below are arena addresses
         dev = feat_img.device
         clips, Lv, H = feat_img.shape
         B = clips * beams
@@ -179,12 +179,9 @@ class KVDecoder:
         resln = None
         self.prefix_qkv, consts = [], []
         for lyr in layers:
-            wqkv16, _, _ = arena.fused_view(lyr.attention.self.query.weight, 3 * H)
-            _, _, bqkv = arena.fused_view(lyr.attention.self.query.bias, 3 * H)
-            c = E.BertLayerFn._layer_consts(lyr, arena, wqkv16, bqkv)
-            x, resln, qkv = E.bert_layer_eval_c(x, resln, lyr, c, self.km, clips, Lv)
+            x, resln, qkv = E.bert_layer_eval_c(x, resln, lyr, self.km, clips, Lv)
             self.prefix_qkv.append(qkv)
-            consts.append(c)
+            consts.append(E._layer_consts(lyr))
         # per-layer text caches and the step's workspaces
         self.cache = [(torch.zeros((B, heads, max_len, 64), dtype=bf16, device=dev), torch.zeros((B, heads, max_len, 64), dtype=bf16, device=dev))
                       for _ in layers]

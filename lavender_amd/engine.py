@@ -9,6 +9,7 @@ bookkeeping only -- no arithmetic runs in ATen.
 `anchor` is a 1-element requires-grad tensor (arena.anchor) threaded through every stage so that autograd runs
 the stage's backward even though its parameters are not autograd inputs.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -17,6 +18,46 @@ import torch
 from . import hip as K
 
 bf16 = torch.bfloat16
+
+# ---- the LAV_* switches of this file ------------------------------------------------------------------------------------
+# Module attributes: tests, bench.py and the tools set them at run time, so every reader takes them at call time.
+# dW = dy^T x is never needed before the optimizer, so it does not have to sit in the dy -> dx dependency chain: issued on
+# a second stream it fills the CUs the main stream leaves idle (partial last rounds of 1-block-per-CU GEMMs, kernel
+# ramps and tails between ~1500 dependent launches per step).  All dW kernels share that ONE stream, so their
+# accumulations into the gradient arena (and the split-K workspace of that stream) stay ordered among themselves.
+_DW_SIDE = os.environ.get("LAV_DW_STREAM", "1") != "0"
+_GQ = 2 if os.environ.get("LAV_GELU_GRAD_U8", "0") != "0" else 1          # GELU' storage: 1 = bf16 (default), 2 = one byte per element (measured 0.8 ms/step SLOWER: the pack / unpack VALU work outweighs the bytes)
+_GQ_DT = torch.uint8 if _GQ == 2 else torch.bfloat16
+_DW_PRIORITY = int(os.environ.get("LAV_DW_PRIORITY", "0"))      # probe hook: HIP priority of the weight-gradient stream (positive = lower than the main stream)
+# fp32 residual stream of the post-LN fusion encoder: the pre-LN sums x + dropout(dense(.)) and the LayerNorm outputs that
+# feed the next residual add stay fp32 (the GEMM operands are the bf16 copies).  Measured on the oracle with bf16 rounding
+# injected (tests/bf16_error_budget.py): this halves the logit error of the full-width model (mean 5.5e-3 -> 2.5e-3, max
+# 3.6e-2 -> 1.6e-2); the same change on the pre-LN Swin stream changes nothing, so the video side stays bf16.
+STREAM32 = os.environ.get("LAV_STREAM32", "1") != "0"
+# Late round 4: that wide stream is stored as fp16 rows, not fp32 -- 11 mantissa bits against bf16's 8 keep the logit error where the fp32
+# stream had it (oracle with the rounding injected, Swin-B + 12 layers: mean |d| 2.65e-3 / max 1.72e-2 with an fp16 stream, 2.56e-3 / 1.64e-2
+# with fp32, 5.49e-3 / 3.55e-2 with bf16) at half the bytes: 69 instead of 138 MB per pre-LayerNorm tensor at the cfg2 shape, read three
+# times and written once per LayerNorm.  Stores saturate at +-65504.  LAV_STREAM_DTYPE=fp32 restores fp32 rows (the reference itself ran
+# fp16 autocast, utils/deepspeed.py:20-51).
+STREAM_DT = torch.float32 if os.environ.get("LAV_STREAM_DTYPE", "fp16") == "fp32" else torch.float16
+# The fp32 copy of a LayerNorm output only ever feeds the NEXT residual add, so it is not written: that GEMM epilogue takes the
+# saved pre-LayerNorm rows + (mean, rstd, gamma, beta) and adds LayerNorm(rows) itself (lav_gemm_epilogue.res_ln_*; same
+# arithmetic, same bits).  138 MB less written per LayerNorm at the cfg2 shape.  LAV_RESLN=0 restores the fp32 LayerNorm output.
+RESLN = STREAM32 and os.environ.get("LAV_RESLN", "1") != "0"
+# Swin blocks whose windows run the persistent kernels (<= 256 tokens, head_dim 32: every Swin-T / Swin-B stage) keep their fused
+# q | k | v projection HEAD-MAJOR -- [q | k | v][head][token][32], written that way by the QKV GEMM epilogue (lav_gemm_epilogue.hm_*) --
+# so that a window's operand pieces are whole 128-byte lines instead of 64-byte halves of the (rows, 3C) rows.  Only the attention
+# kernels read qkv (its gradient dqkv stays row-major: it is a GEMM operand).  LAV_QKV_HEADMAJOR=0 restores the row-major layout.
+QKV_HEADMAJOR = os.environ.get("LAV_QKV_HEADMAJOR", "1") != "0"
+# Fusion-encoder layers through the stage-level C entries (lav_bert_layer_fwd / _bwd, csrc/stages.cpp): one host -> C transition per
+# layer pass instead of 7 (forward) / 15 (backward); the same kernels with the same arguments, bit-identical results.  Applies to the
+# default configuration (fp32 residual stream with the recomputed-LayerNorm residual, bf16 GELU') of every layer that does not read its
+# input through the pair map.  LAV_STAGE_C=0 restores the per-kernel path.
+STAGE_C = os.environ.get("LAV_STAGE_C", "1") != "0"
+_FUSION_SRC = os.environ.get("LAV_FUSION_SRC", "1") != "0"       # 0: separate feat_img / feat_txt buffers + T.cat in front of the fusion encoder (A/B baseline)
+# the first fusion layer reads its input THROUGH the pair map (lav_gemm_epilogue.a_rowmap / res_rowmap) instead of a gathered
+# (pairs, L, H) copy; needs the 256-column GEMM tiles.  LAV_PAIR_FUSED=0 restores the materialised gather (PairSeqFn).
+PAIR_FUSED = os.environ.get("LAV_PAIR_FUSED", "1") != "0"
 
 
 def W16(p):
@@ -77,41 +118,7 @@ def register_arena(a):
     _arenas.append(weakref.ref(a))
 
 
-# ---- weight-gradient GEMMs on a side stream --------------------------------------------------------------------------
-# dW = dy^T x is never needed before the optimizer, so it does not have to sit in the dy -> dx dependency chain: issued on
-# a second stream it fills the CUs the main stream leaves idle (partial last rounds of 1-block-per-CU GEMMs, kernel
-# ramps and tails between ~1500 dependent launches per step).  All dW kernels share that ONE stream, so their
-# accumulations into the gradient arena (and the split-K workspace of that stream) stay ordered among themselves.
-_DW_SIDE = os.environ.get("LAV_DW_STREAM", "1") != "0"
-_GQ = 2 if os.environ.get("LAV_GELU_GRAD_U8", "0") != "0" else 1          # GELU' storage: 1 = bf16 (default), 2 = one byte per element (measured 0.8 ms/step SLOWER: the pack / unpack VALU work outweighs the bytes)
-_GQ_DT = torch.uint8 if _GQ == 2 else torch.bfloat16
 _dw_streams = {}
-_DW_PRIORITY = int(os.environ.get("LAV_DW_PRIORITY", "0"))      # probe hook: HIP priority of the weight-gradient stream (positive = lower than the main stream)
-# fp32 residual stream of the post-LN fusion encoder: the pre-LN sums x + dropout(dense(.)) and the LayerNorm outputs that
-# feed the next residual add stay fp32 (the GEMM operands are the bf16 copies).  Measured on the oracle with bf16 rounding
-# injected (tests/bf16_error_budget.py): this halves the logit error of the full-width model (mean 5.5e-3 -> 2.5e-3, max
-# 3.6e-2 -> 1.6e-2); the same change on the pre-LN Swin stream changes nothing, so the video side stays bf16.
-STREAM32 = os.environ.get("LAV_STREAM32", "1") != "0"
-# Late round 4: that wide stream is stored as fp16 rows, not fp32 -- 11 mantissa bits against bf16's 8 keep the logit error where the fp32
-# stream had it (oracle with the rounding injected, Swin-B + 12 layers: mean |d| 2.65e-3 / max 1.72e-2 with an fp16 stream, 2.56e-3 / 1.64e-2
-# with fp32, 5.49e-3 / 3.55e-2 with bf16) at half the bytes: 69 instead of 138 MB per pre-LayerNorm tensor at the cfg2 shape, read three
-# times and written once per LayerNorm.  Stores saturate at +-65504.  LAV_STREAM_DTYPE=fp32 restores fp32 rows (the reference itself ran
-# fp16 autocast, utils/deepspeed.py:20-51).
-STREAM_DT = torch.float32 if os.environ.get("LAV_STREAM_DTYPE", "fp16") == "fp32" else torch.float16
-# The fp32 copy of a LayerNorm output only ever feeds the NEXT residual add, so it is not written: that GEMM epilogue takes the
-# saved pre-LayerNorm rows + (mean, rstd, gamma, beta) and adds LayerNorm(rows) itself (lav_gemm_epilogue.res_ln_*; same
-# arithmetic, same bits).  138 MB less written per LayerNorm at the cfg2 shape.  LAV_RESLN=0 restores the fp32 LayerNorm output.
-RESLN = STREAM32 and os.environ.get("LAV_RESLN", "1") != "0"
-# Swin blocks whose windows run the persistent kernels (<= 256 tokens, head_dim 32: every Swin-T / Swin-B stage) keep their fused
-# q | k | v projection HEAD-MAJOR -- [q | k | v][head][token][32], written that way by the QKV GEMM epilogue (lav_gemm_epilogue.hm_*) --
-# so that a window's operand pieces are whole 128-byte lines instead of 64-byte halves of the (rows, 3C) rows.  Only the attention
-# kernels read qkv (its gradient dqkv stays row-major: it is a GEMM operand).  LAV_QKV_HEADMAJOR=0 restores the row-major layout.
-QKV_HEADMAJOR = os.environ.get("LAV_QKV_HEADMAJOR", "1") != "0"
-# Fusion-encoder layers through the stage-level C entries (lav_bert_layer_fwd / _bwd, csrc/stages.cpp): one host -> C transition per
-# layer pass instead of 7 (forward) / 15 (backward); the same kernels with the same arguments, bit-identical results.  Applies to the
-# default configuration (fp32 residual stream with the recomputed-LayerNorm residual, bf16 GELU') of every layer that does not read its
-# input through the pair map.  LAV_STAGE_C=0 restores the per-kernel path.
-STAGE_C = os.environ.get("LAV_STAGE_C", "1") != "0"
 
 
 def dw_stream(device):
@@ -121,18 +128,25 @@ def dw_stream(device):
     return st
 
 
-def dw_gemm(A, Bm, M, N, Kd, **kw):
-    """layout-2 GEMM accumulating into the gradient arena; A / Bm may be freed by the caller right after this returns."""
-    if not _DW_SIDE:
-        return K.gemm(2, A, Bm, M, N, Kd, **kw)
-    side = dw_stream(A.device)
+def on_dw_stream(device, fn, tensors):
+    """fn() on the weight-gradient stream of `device`, behind everything the current stream holds; the join at the end of the backward is armed
+    and `tensors` (what fn's kernels touch; None entries are skipped) are recorded on that stream, so the caller may free them right after this
+    returns.  With LAV_DW_STREAM=0 (read here, at call time) or off the GPU fn() runs in place."""
+    if not _DW_SIDE or device.type != "cuda":
+        return fn()
+    side = dw_stream(device)
     _arm_join()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        K.gemm(2, A, Bm, M, N, Kd, **kw)
-    for t in (A, Bm, kw.get("k_keep")):
+        fn()
+    for t in tensors:
         if t is not None:
             t.record_stream(side)
+
+
+def dw_gemm(A, Bm, M, N, Kd, **kw):
+    """layout-2 GEMM accumulating into the gradient arena; A / Bm may be freed by the caller right after this returns."""
+    on_dw_stream(A.device, lambda: K.gemm(2, A, Bm, M, N, Kd, **kw), (A, Bm, kw.get("k_keep")))
 
 
 class DwGroup:
@@ -151,17 +165,21 @@ class DwGroup:
         self.jobs.append(dict(A=A, B=Bm, M=M, N=N, out=out, rowsum_a=rowsum_a, fallback_splits=splits, assign=assign))
 
     def launch(self, device):
-        if not self.jobs:
-            return
-        side = dw_stream(device)
-        _arm_join()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            K.gemm_tn_grouped(self.jobs, self.gs)
-        for j in self.jobs:
-            j["A"].record_stream(side)
-            j["B"].record_stream(side)
-        self.jobs = []
+        if self.jobs:
+            on_dw_stream(device, lambda: K.gemm_tn_grouped(self.jobs, self.gs), [j[k] for j in self.jobs for k in "AB"])
+            self.jobs = []
+
+
+def _stage_bwd(entry, fields, shapes, splits, gs, device, operands):
+    """a stage-level backward entry (K.swin_block_bwd / K.bert_layer_bwd): it issues the stage's weight-gradient GEMMs on the weight-gradient
+    stream itself (None: in line), so their `operands` are recorded there -- not to be recycled before that stream ran"""
+    side = dw_stream(device) if _DW_SIDE else None
+    raw = side.cuda_stream if side is not None else None
+    _arm_join()
+    K.ensure_stage_workspaces(shapes, splits, gs, raw)
+    entry(fields, raw)
+    for t in operands if side is not None else ():
+        t.record_stream(side)
 
 
 def ln_bwd(dy, *args, **kw):
@@ -277,6 +295,72 @@ class PatchEmbedFn(torch.autograd.Function):
         return None, None, None, None
 
 
+# ---- lav_swin_block_desc / lav_swin_block_bwd_desc: values labelled by field name, placed by K.SB_FWD / K.SB_BWD -------------------------
+_SB_PARAMS = ("ln1_gamma", "ln1_beta", "w_qkv", "b_qkv", "w_proj", "b_proj", "ln2_gamma", "ln2_beta", "w_fc1", "b_fc1", "w_fc2", "b_fc2")
+_SB_FWD_NAMES = ("rows", "C", "heads", "rows_per_group", "qkv_headmajor", "ln_eps", "attn") + _SB_PARAMS + (
+    "dp_attn", "dp_mlp", "x", "y1", "mean1", "rstd1", "mean2", "rstd2", "qkv", "ao", "lse", "x_mid", "y2", "h_pre", "h", "out")
+_SB_BWD_CONSTS = ("wt_qkv", "wt_proj", "wt_fc1", "wt_fc2", "ldt_qkv", "ldt_proj", "ldt_fc1", "ldt_fc2", "g_ln1_gamma", "g_ln1_beta", "g_w_qkv",
+                  "g_b_qkv", "g_bias_table", "g_w_proj", "g_b_proj", "g_ln2_gamma", "g_ln2_beta", "g_w_fc1", "g_b_fc1", "g_w_fc2", "g_b_fc2")
+_SB_BWD_NAMES = _SB_FWD_NAMES + ("dy", "alpha_attn", "alpha_mlp") + _SB_BWD_CONSTS + ("splits_qkv", "splits_proj", "splits_fc1", "splits_fc2") + (
+    "dh", "d_y2", "d_mid", "d_ao", "dqkv", "d_y1", "dx", "group_splits", "assign_mask")
+_SB_FWD_PLACE, _SB_BWD_PLACE = K.SB_FWD.placer(_SB_FWD_NAMES), K.SB_BWD.placer(_SB_BWD_NAMES)
+
+
+def _stage_consts(owner, arena, params, wt, grads, **more):
+    """The cached constants of a stage on `owner` (a Swin block, a fusion layer): `params` = the device addresses of its parameter tensors,
+    `bwd` = those of the transposed weight copies `wt`, their row strides, and the gradient accumulators `grads`.  All are arena views, fixed
+    for the arena's life: the cache is keyed on the arena."""
+    dp = lambda ts: tuple(t.data_ptr() for t in ts)
+    consts = dict(params=dp(params), bwd=dp(wt) + tuple(K._ld(t) for t in wt) + dp(grads), **more)
+    owner.__dict__["_lav_stage_consts"] = (arena, consts)
+    return consts
+
+
+def _block_consts(blk, arena):
+    """a Swin block's `params` (labelled _SB_PARAMS) and `bwd` (labelled _SB_BWD_CONSTS) addresses"""
+    c = blk.__dict__.get("_lav_stage_consts")
+    if c is not None and c[0] is arena:
+        return c[1]
+    a, mlp, n1, n2 = blk.attn, blk.mlp, blk.norm1, blk.norm2
+    mats = (a.qkv.weight, a.proj.weight, mlp.fc1.weight, mlp.fc2.weight)
+    params = (n1.weight.data, n1.bias.data, W16(a.qkv.weight), a.qkv.bias.data, W16(a.proj.weight), a.proj.bias.data, n2.weight.data, n2.bias.data,
+              W16(mlp.fc1.weight), mlp.fc1.bias.data, W16(mlp.fc2.weight), mlp.fc2.bias.data)
+    grads = (n1.weight, n1.bias, a.qkv.weight, a.qkv.bias, a.relative_position_bias_table, a.proj.weight, a.proj.bias, n2.weight, n2.bias,
+             mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)
+    assert len(params) == len(_SB_PARAMS) and 2 * len(mats) + len(grads) == len(_SB_BWD_CONSTS)
+    return _stage_consts(blk, arena, params, [W16T(p) for p in mats], [GR(p) for p in grads])
+
+
+def _window_attn(blk, geo, C, grid):
+    """(the window K.Attn of a Swin block on the (D, H, W) `grid`, head-major qkv or not)"""
+    heads = blk.num_heads
+    win, sh, cfg = geo["window"], geo["shift"], geo["cfg_window"]
+    hm = QKV_HEADMAJOR and C // heads == 32 and win[0] * win[1] * win[2] <= 256
+    att = K.Attn(0, heads, C // heads, B=geo["B"], D=grid[0], H=grid[1], W=grid[2], wd=win[0], wh=win[1], ww=win[2], sd=sh[0], sh=sh[1],
+                 sw=sh[2], cfg_wd=cfg[0], cfg_wh=cfg[1], cfg_ww=cfg[2], bias_table=blk.attn.relative_position_bias_table.data,
+                 qkv_headmajor=int(hm))
+    return att, hm
+
+
+def _keep_swin_ctx(ctx, blk, att, rpg, geo, dp_attn, pad):
+    ctx.blk, ctx.att, ctx.rpg, ctx.pad = blk, att, rpg, pad
+    ctx.notify, ctx.arena = geo.get("notify"), geo.get("arena")     # notify: first block of a stage, its backward completes the stage's gradients
+    ctx.has_dp, ctx.keep_attn = dp_attn is not None, float(blk.keep_prob) if dp_attn is not None else 1.0
+
+
+def _stat_rows(st, n):
+    """addresses of the n rows (mean, rstd, ...) of a statistics tensor; NULLs when nothing was kept"""
+    return tuple(r.data_ptr() for r in st.unbind(0)) if st is not None else (0,) * n
+
+
+def _swin_fwd_values(head, dp_attn, dp_mlp, x, y1, st, qkv, ao, lse, x_mid, y2, h_pre, h, out_ptr):
+    """lav_swin_block_desc, labelled _SB_FWD_NAMES.  head: the scalars, the window descriptor's address and the parameter addresses;
+    st: the (4, rows) statistics mean1, rstd1, mean2, rstd2.  Called on the fresh tensors (forward) and on the unpacked saved ones (backward)."""
+    dp = K._dp
+    return head + (dp(dp_attn), dp(dp_mlp), x.data_ptr(), y1.data_ptr()) + _stat_rows(st, 4) + (
+        qkv.data_ptr(), ao.data_ptr(), dp(lse), x_mid.data_ptr(), y2.data_ptr(), dp(h_pre), h.data_ptr(), out_ptr)
+
+
 class SwinBlockFn(torch.autograd.Function):
     """SwinTransformerBlock3D.forward (video_swin.py:204-261) on (M, C) channels-last tokens."""
 
@@ -288,8 +372,7 @@ class SwinBlockFn(torch.autograd.Function):
         rpg = M // B
         a, mlp = blk.attn, blk.mlp
         keep = _keep(ctx)
-        win, sh, cfg = geo["window"], geo["shift"], geo["cfg_window"]
-        pad = pad_maps(x.device, B, (D, H, Wd), win)
+        pad = pad_maps(x.device, B, (D, H, Wd), geo["window"])
         if STAGE_C and pad is None and _GQ == 1 and x.is_contiguous():
             return SwinBlockFn._forward_c(ctx, x, blk, geo, dp_attn, dp_mlp, keep)
         y1, mean1, rstd1 = K.layernorm_fwd(x, M, C, blk.norm1.weight.data, blk.norm1.bias.data, 1e-5, want_stats=keep)
@@ -300,11 +383,8 @@ class SwinBlockFn(torch.autograd.Function):
             y1 = K.gather_rows(y1, to_pad, Ma, C)
         else:
             Ma = M
-        hm = QKV_HEADMAJOR and C // heads == 32 and win[0] * win[1] * win[2] <= 256
+        att, hm = _window_attn(blk, geo, C, (D, H, Wd))
         qkv = K.gemm(0, y1, W16(a.qkv.weight), Ma, 3 * C, C, bias=a.qkv.bias.data, headmajor=(heads, 32) if hm else None)
-        att = K.Attn(0, heads, C // heads, B=B, D=D, H=H, W=Wd, wd=win[0], wh=win[1], ww=win[2], sd=sh[0], sh=sh[1],
-                     sw=sh[2], cfg_wd=cfg[0], cfg_wh=cfg[1], cfg_ww=cfg[2], bias_table=a.relative_position_bias_table.data,
-                     qkv_headmajor=int(hm))
         lse = torch.empty(att.lse_elems(), dtype=torch.float32, device=x.device) if keep else None
         ao = torch.empty((Ma, C), dtype=bf16, device=x.device)
         att.fwd(qkv, ao, lse)
@@ -319,12 +399,7 @@ class SwinBlockFn(torch.autograd.Function):
         out = K.gemm(0, h, W16(mlp.fc2.weight), M, C, 4 * C, bias=mlp.fc2.bias.data, row_scale=dp_mlp, rows_per_group=rpg,
                      residual=x_mid)
         if keep:
-            ctx.blk, ctx.att, ctx.rpg = blk, att, rpg
-            ctx.notify = geo.get("notify")               # first block of a stage: its backward completes the stage's gradients
-            ctx.arena = geo.get("arena")
-            ctx.keep_attn = float(blk.keep_prob) if dp_attn is not None else 1.0
-            ctx.has_dp = dp_attn is not None
-            ctx.pad = pad
+            _keep_swin_ctx(ctx, blk, att, rpg, geo, dp_attn, pad)
             ctx.save_for_backward(x, y1, mean1, rstd1, qkv, ao, lse, x_mid, y2, mean2, rstd2, h_pre, h,
                                   dp_attn if dp_attn is not None else x.new_empty(0),
                                   dp_mlp if dp_mlp is not None else x.new_empty(0),
@@ -332,96 +407,52 @@ class SwinBlockFn(torch.autograd.Function):
         return out
 
     @staticmethod
-    def _block_consts(blk, arena):
-        c = blk.__dict__.get("_lav_stage_consts")
-        if c is not None and c[0] is arena:
-            return c[1]
-        a, mlp = blk.attn, blk.mlp
-        dp = lambda t: t.data_ptr()
-        params = (dp(blk.norm1.weight.data), dp(blk.norm1.bias.data), dp(W16(a.qkv.weight)), dp(a.qkv.bias.data), dp(W16(a.proj.weight)),
-                  dp(a.proj.bias.data), dp(blk.norm2.weight.data), dp(blk.norm2.bias.data), dp(W16(mlp.fc1.weight)), dp(mlp.fc1.bias.data),
-                  dp(W16(mlp.fc2.weight)), dp(mlp.fc2.bias.data))
-        wt = (W16T(a.qkv.weight), W16T(a.proj.weight), W16T(mlp.fc1.weight), W16T(mlp.fc2.weight))
-        bwd = tuple(dp(t) for t in wt) + tuple(K._ld(t) for t in wt) + (
-            dp(GR(blk.norm1.weight)), dp(GR(blk.norm1.bias)), dp(GR(a.qkv.weight)), dp(GR(a.qkv.bias)), dp(GR(a.relative_position_bias_table)),
-            dp(GR(a.proj.weight)), dp(GR(a.proj.bias)), dp(GR(blk.norm2.weight)), dp(GR(blk.norm2.bias)), dp(GR(mlp.fc1.weight)), dp(GR(mlp.fc1.bias)),
-            dp(GR(mlp.fc2.weight)), dp(GR(mlp.fc2.bias)))
-        consts = dict(params=params, bwd=bwd)
-        blk.__dict__["_lav_stage_consts"] = (arena, consts)
-        return consts
-
-    @staticmethod
     def _forward_c(ctx, x, blk, geo, dp_attn, dp_mlp, keep):
         """the seven launches of the block (grid a multiple of the window) through ONE call of lav_swin_block_fwd"""
-        import ctypes as C
         M, Cn = x.shape
-        heads = blk.num_heads
-        B, D, H, Wd = geo["B"], geo["D"], geo["H"], geo["W"]
-        rpg = M // B
-        a = blk.attn
-        win, sh, cfg = geo["window"], geo["shift"], geo["cfg_window"]
-        c = SwinBlockFn._block_consts(blk, geo.get("arena"))
-        hm = QKV_HEADMAJOR and Cn // heads == 32 and win[0] * win[1] * win[2] <= 256
-        att = K.Attn(0, heads, Cn // heads, B=B, D=D, H=H, W=Wd, wd=win[0], wh=win[1], ww=win[2], sd=sh[0], sh=sh[1],
-                     sw=sh[2], cfg_wd=cfg[0], cfg_wh=cfg[1], cfg_ww=cfg[2], bias_table=a.relative_position_bias_table.data,
-                     qkv_headmajor=int(hm))
-        dev, f32 = x.device, torch.float32
-        e = torch.empty
+        rpg = M // geo["B"]
+        c = _block_consts(blk, geo.get("arena"))
+        att, hm = _window_attn(blk, geo, Cn, (geo["D"], geo["H"], geo["W"]))
+        dev, e = x.device, torch.empty
         y1, ao, x_mid, y2, out = (e((M, Cn), dtype=bf16, device=dev) for _ in range(5))
         qkv, h = e((M, 3 * Cn), dtype=bf16, device=dev), e((M, 4 * Cn), dtype=bf16, device=dev)
         st = lse = h_pre = None
-        p_st = 0
         if keep:
-            st = e((4, M), dtype=f32, device=dev)           # mean1, rstd1, mean2, rstd2
-            p_st = st.data_ptr()
-            lse = e(att.lse_elems(), dtype=f32, device=dev)
+            st = e((4, M), dtype=torch.float32, device=dev)           # mean1, rstd1, mean2, rstd2
+            lse = e(att.lse_elems(), dtype=torch.float32, device=dev)
             h_pre = e((M, 4 * Cn), dtype=bf16, device=dev)
-        fields = (M, Cn, heads, rpg, int(hm), 1e-5, C.addressof(att.d)) + c["params"] + (
-            K._dp(dp_attn), K._dp(dp_mlp), x.data_ptr(), y1.data_ptr(), p_st, p_st + 4 * M if keep else 0, qkv.data_ptr(), ao.data_ptr(), K._dp(lse),
-            x_mid.data_ptr(), y2.data_ptr(), p_st + 8 * M if keep else 0, p_st + 12 * M if keep else 0, K._dp(h_pre), h.data_ptr(), out.data_ptr())
-        K.swin_block_fwd(fields)
+        head = (M, Cn, blk.num_heads, rpg, int(hm), 1e-5, ctypes.addressof(att.d)) + c["params"]
+        K.swin_block_fwd(_SB_FWD_PLACE(_swin_fwd_values(head, dp_attn, dp_mlp, x, y1, st, qkv, ao, lse, x_mid, y2, h_pre, h, out.data_ptr())))
         if keep:
-            ctx.blk, ctx.att, ctx.rpg = blk, att, rpg
-            ctx.notify = geo.get("notify")
-            ctx.arena = geo.get("arena")
-            ctx.keep_attn = float(blk.keep_prob) if dp_attn is not None else 1.0
-            ctx.has_dp = dp_attn is not None
-            ctx.pad = None
+            # ctx.att: the window K.Attn must outlive the backward -- its address is inside the descriptor head
+            _keep_swin_ctx(ctx, blk, att, rpg, geo, dp_attn, None)
             # the backward rebuilds the activation addresses from the UNPACKED saved tensors (saved-tensor hooks may move them); kept from
-            # here: the scalar / parameter head of the descriptor and the address of the block output (never read by the backward)
-            ctx.c_stage, ctx.c_head, ctx.c_out, ctx.c_consts = True, fields[:7 + len(c["params"])], out.data_ptr(), c
+            # here: the scalar / parameter head of the descriptor, the address of the block output (never read by the backward) and
+            # c_consts, the FORWARD's constants (not re-queried in the backward: the cache may have been rebuilt since)
+            ctx.c_stage, ctx.c_head, ctx.c_out, ctx.c_consts = True, head, out.data_ptr(), c
             ctx.save_for_backward(x, y1, st, qkv, ao, lse, x_mid, y2, h_pre, h,
                                   dp_attn if dp_attn is not None else x.new_empty(0), dp_mlp if dp_mlp is not None else x.new_empty(0))
         return out
 
     @staticmethod
     def _backward_c(ctx, dy):
-        blk, att = ctx.blk, ctx.att
+        blk = ctx.blk
         x, y1, st, qkv, ao, lse, x_mid, y2, h_pre, h, dp_attn, dp_mlp = ctx.saved_tensors
-        M, Cn = x.shape
-        dev = x.device
-        e = torch.empty
+        has_dp = ctx.has_dp
+        if not has_dp:
+            dp_attn = dp_mlp = None
+        (M, Cn), dev, e = x.shape, x.device, torch.empty
         d_y2, d_mid, d_ao, d_y1, dx = (e((M, Cn), dtype=bf16, device=dev) for _ in range(5))
         dh, dqkv = e((M, 4 * Cn), dtype=bf16, device=dev), e((M, 3 * Cn), dtype=bf16, device=dev)
         alpha = 1.0 / ctx.keep_attn
         am = (blk.mlp.fc2.weight, blk.mlp.fc1.weight, blk.attn.proj.weight, blk.attn.qkv.weight)      # order of lav_swin_block_bwd_desc.assign_mask
-        has_dp = ctx.has_dp
         splits = (K.splits_for(3 * Cn, Cn, M), K.splits_for(Cn, Cn, M, has_dp), K.splits_for(4 * Cn, Cn, M), K.splits_for(Cn, 4 * Cn, M, has_dp))
-        b = ctx.c_consts["bwd"]
         gs = K.group_splits_for(((Cn, 4 * Cn), (4 * Cn, Cn), (Cn, Cn), (3 * Cn, Cn)), M)
-        p_st = st.data_ptr()
-        ffields = ctx.c_head + (
-            K._dp(dp_attn if has_dp else None), K._dp(dp_mlp if has_dp else None), x.data_ptr(), y1.data_ptr(), p_st, p_st + 4 * M, qkv.data_ptr(), ao.data_ptr(),
-            lse.data_ptr(), x_mid.data_ptr(), y2.data_ptr(), p_st + 8 * M, p_st + 12 * M, h_pre.data_ptr(), h.data_ptr(), ctx.c_out)
-        fields = ffields + (dy.data_ptr(), alpha, alpha) + b[:21] + splits + (
-            dh.data_ptr(), d_y2.data_ptr(), d_mid.data_ptr(), d_ao.data_ptr(), dqkv.data_ptr(), d_y1.data_ptr(), dx.data_ptr(), gs, _assign_mask(am))
-        side = dw_stream(dev) if _DW_SIDE else None
-        _arm_join()
-        K.ensure_stage_workspaces(((3 * Cn, Cn), (Cn, Cn), (4 * Cn, Cn), (Cn, 4 * Cn)), splits, gs, side.cuda_stream if side is not None else None)
-        K.swin_block_bwd(fields, side.cuda_stream if side is not None else None)
-        if side is not None:
-            for t in (dy, h, dh, y2, d_mid, ao, dqkv, y1, qkv, d_ao, lse) + ((dp_attn, dp_mlp) if has_dp else ()):
-                t.record_stream(side)
+        fwd = _swin_fwd_values(ctx.c_head, dp_attn, dp_mlp, x, y1, st, qkv, ao, lse, x_mid, y2, h_pre, h, ctx.c_out)
+        fields = _SB_BWD_PLACE(fwd + (dy.data_ptr(), alpha, alpha) + ctx.c_consts["bwd"] + splits + tuple(
+            t.data_ptr() for t in (dh, d_y2, d_mid, d_ao, dqkv, d_y1, dx)) + (gs, _assign_mask(am)))       # labelled _SB_BWD_NAMES
+        _stage_bwd(K.swin_block_bwd, fields, ((3 * Cn, Cn), (Cn, Cn), (4 * Cn, Cn), (Cn, 4 * Cn)), splits, gs, dev,
+                   (dy, h, dh, y2, d_mid, ao, dqkv, y1, qkv, d_ao, lse) + ((dp_attn, dp_mlp) if has_dp else ()))
         if ctx.notify and ctx.arena is not None:
             ctx.arena.notify(ctx.notify)
         return None, dx, None, None, None, None
@@ -463,12 +494,7 @@ class SwinBlockFn(torch.autograd.Function):
             # the relative-position-bias gradient is a parameter gradient: its kernel (it re-derives dS from qkv, dO, lse and
             # the -delta the dQ pass leaves behind the lse) runs on the weight-gradient stream, off the dy -> dx chain
             att.bwd(qkv, ao, d_ao, lse, dqkv, None)
-            side = dw_stream(qkv.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                att.bwd_bias(qkv, d_ao, lse, G(a.relative_position_bias_table))
-            for t in (qkv, d_ao, lse):
-                t.record_stream(side)
+            on_dw_stream(qkv.device, lambda: att.bwd_bias(qkv, d_ao, lse, G(a.relative_position_bias_table)), (qkv, d_ao, lse))
         else:
             att.bwd(qkv, ao, d_ao, lse, dqkv, G(a.relative_position_bias_table))
         dw_gemm(dqkv, y1, 3 * C, C, Ma, **_gw(a.qkv.weight), splits=K.splits_for(3 * C, C, Ma),
@@ -547,12 +573,19 @@ class LayerNormFn(torch.autograd.Function):
 # leaves the buffer as "pending"; TextEmbedFn, when its n * X rows are exactly that tail, writes them behind.  feat_img / feat_txt are views of the
 # one buffer, and JoinRowsFn hands the whole of it to the first fusion layer without the T.cat of model.py:235 (no copy forward, no split backward).
 _fusion_tail = {"hint": 0, "pending": None}
-_FUSION_SRC = os.environ.get("LAV_FUSION_SRC", "1") != "0"       # 0: separate feat_img / feat_txt buffers + T.cat in front of the fusion encoder (A/B baseline)
 
 
 def fusion_tail_hint(rows):
     _fusion_tail["hint"] = int(rows) if _FUSION_SRC else 0
     _fusion_tail["pending"] = None
+
+
+def _claim_fusion_tail(rows, Hd, device):
+    """the tail of the video rows' buffer when exactly `rows` rows of width Hd are pending on `device`, else None; nothing stays pending"""
+    pend, _fusion_tail["pending"] = _fusion_tail["pending"], None
+    if pend is not None and pend[2] == rows and pend[0].shape[1] == Hd and pend[0].device == device:
+        return pend[0][pend[1]:]
+    return None
 
 
 class JoinRowsFn(torch.autograd.Function):
@@ -634,10 +667,7 @@ class TextEmbedFn(torch.autograd.Function):
         Hd = emb.word_embeddings.weight.shape[1]
         ids = ids.contiguous()
         seed = K.next_seed()
-        pend, out = _fusion_tail["pending"], None
-        _fusion_tail["pending"] = None
-        if pend is not None and pend[2] == n * X and pend[0].shape[1] == Hd and pend[0].device == ids.device:
-            out = pend[0][pend[1]:]                              # the tail of the video rows' buffer
+        out = _claim_fusion_tail(n * X, Hd, ids.device)
         out, mean, rstd = K.text_embed_fwd(ids, n, X, Hd, emb.word_embeddings.weight.data, emb.position_embeddings.weight.data,
                                            emb.token_type_embeddings.weight.data, emb.LayerNorm.weight.data,
                                            emb.LayerNorm.bias.data, emb.LayerNorm.eps, dropout_p, seed, out=out)
@@ -656,20 +686,11 @@ class TextEmbedFn(torch.autograd.Function):
                 emb.token_type_embeddings.weight.data, emb.LayerNorm.weight.data, mean, rstd, ctx.p, ctx.seed,
                 G(emb.word_embeddings.weight), G(emb.position_embeddings.weight), G(emb.token_type_embeddings.weight),
                 G(emb.LayerNorm.weight), G(emb.LayerNorm.bias))
-        if _DW_SIDE and dout.is_cuda:
-            # Only parameter gradients come out of this kernel, so it runs on the WEIGHT-GRADIENT stream: the word-embedding gradient is also
-            # written by the tied decoder's weight-gradient GEMM there (an assign when it is the step's first writer, a read-modify-write otherwise)
-            # and the stream's FIFO order puts these atomics behind it.  (Autograd runs this node right after the fusion backward, before the
-            # Swin backward: making the MAIN stream wait for the weight-gradient stream here stalled it for 0.6 ms per step.)
-            side = dw_stream(dout.device)
-            _arm_join()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                K.text_embed_bwd(*args)
-            for t in (ids, dout, mean, rstd):
-                t.record_stream(side)
-        else:
-            K.text_embed_bwd(*args)
+        # Only parameter gradients come out of this kernel, so it runs on the WEIGHT-GRADIENT stream: the word-embedding gradient is also
+        # written by the tied decoder's weight-gradient GEMM there (an assign when it is the step's first writer, a read-modify-write otherwise)
+        # and the stream's FIFO order puts these atomics behind it.  (Autograd runs this node right after the fusion backward, before the
+        # Swin backward: making the MAIN stream wait for the weight-gradient stream here stalled it for 0.6 ms per step.)
+        on_dw_stream(dout.device, lambda: K.text_embed_bwd(*args), (ids, dout, mean, rstd))
         return None, None, None, None
 
 
@@ -697,10 +718,7 @@ class PreTextEmbedFn(torch.autograd.Function):
             stride = 0 if src.shape[0] == 1 else Lp * Hd
             assert src.dtype == bf16 and src.shape[-1] == Hd and src.shape[0] in (1, n), (tuple(src.shape), n)
         seed = K.next_seed()
-        pend, out = _fusion_tail["pending"], None
-        _fusion_tail["pending"] = None
-        if pend is not None and pend[2] == n * (Lp + X) and pend[0].shape[1] == Hd and pend[0].device == ids.device:
-            out = pend[0][pend[1]:]                              # the tail of the video rows' buffer
+        out = _claim_fusion_tail(n * (Lp + X), Hd, ids.device)
         out, mean, rstd = K.text_embed_pre_fwd(ids, n, Lp, X, Hd, emb.word_embeddings.weight.data, emb.position_embeddings.weight.data,
                                                emb.token_type_embeddings.weight.data, emb.LayerNorm.weight.data, emb.LayerNorm.bias.data,
                                                emb.LayerNorm.eps, dropout_p, seed, src, stride, out=out)
@@ -725,18 +743,9 @@ class PreTextEmbedFn(torch.autograd.Function):
                 emb.token_type_embeddings.weight.data, emb.LayerNorm.weight.data, mean, rstd, ctx.p, ctx.seed,
                 G(emb.word_embeddings.weight), G(emb.position_embeddings.weight), G(emb.token_type_embeddings.weight),
                 G(emb.LayerNorm.weight), G(emb.LayerNorm.bias), stride, d_pre, mode)
-        if _DW_SIDE and dout.is_cuda:
-            # the stream placement of TextEmbedFn.backward (see there).  A prompt's d_pre is written on the weight-gradient stream too; its one
-            # reader is the prompt's own TextEmbedFn.backward, which runs on that stream after this kernel (FIFO order).
-            side = dw_stream(dout.device)
-            _arm_join()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                K.text_embed_pre_bwd(*args)
-            for t in (ids, dout, mean, rstd, d_pre):
-                t.record_stream(side)
-        else:
-            K.text_embed_pre_bwd(*args)
+        # the stream placement of TextEmbedFn.backward (see there).  A prompt's d_pre is written on the weight-gradient stream too; its one
+        # reader is the prompt's own TextEmbedFn.backward, which runs on that stream after this kernel (FIFO order).
+        on_dw_stream(dout.device, lambda: K.text_embed_pre_bwd(*args), (ids, dout, mean, rstd, d_pre))
         return None, None, None, None, (d_pre if ctx.task is None else None), None
 
 
@@ -774,11 +783,6 @@ def pair_csr(flat, n_src):
     order = np.argsort(flat, kind="stable").astype(np.int32)
     start = np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=n_src))]).astype(np.int32)
     return start, order
-
-
-# the first fusion layer reads its input THROUGH the pair map (lav_gemm_epilogue.a_rowmap / res_rowmap) instead of a gathered
-# (pairs, L, H) copy; needs the 256-column GEMM tiles.  LAV_PAIR_FUSED=0 restores the materialised gather (PairSeqFn).
-PAIR_FUSED = os.environ.get("LAV_PAIR_FUSED", "1") != "0"
 
 
 def pair_fused_ok(Hd):
@@ -839,6 +843,51 @@ class RowGatherFn(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------
 # fusion encoder layer / MLM head / loss
 # ---------------------------------------------------------------------------------------------------
+# ---- lav_bert_layer_desc / lav_bert_layer_bwd_desc: values labelled by field name, placed by K.BL_FWD / K.BL_BWD -----------------------
+_BL_PARAMS = ("w_qkv", "b_qkv", "w_ao", "b_ao", "ln1_gamma", "ln1_beta", "w_ff1", "b_ff1", "w_ff2", "b_ff2", "ln2_gamma", "ln2_beta")
+_BL_FWD_NAMES = ("n_seq", "L", "hidden", "heads", "ffn", "p_hidden", "p_attn", "ln_eps", "seed_attn", "seed1", "seed2", "causal_from", "stream_f16",
+                 "ln2_eps") + _BL_PARAMS + ("key_mask", "x", "res_pre", "res_mean", "res_rstd", "res_gamma", "res_beta", "qkv", "cx", "lse", "pre1",
+                                            "mean1", "rstd1", "x1", "h_pre", "h", "pre2", "mean2", "rstd2", "y")
+_BL_BWD_CONSTS = ("wt_qkv", "wt_ao", "wt_ff1", "wt_ff2", "ldt_qkv", "ldt_ao", "ldt_ff1", "ldt_ff2", "g_w_qkv", "g_b_qkv", "g_w_ao", "g_b_ao",
+                  "g_ln1_gamma", "g_ln1_beta", "g_w_ff1", "g_b_ff1", "g_w_ff2", "g_b_ff2", "g_ln2_gamma", "g_ln2_beta")
+_BL_BWD_NAMES = _BL_FWD_NAMES + ("dy",) + _BL_BWD_CONSTS + ("splits_qkv", "splits_ao", "splits_ff1", "splits_ff2") + (
+    "d_pre2", "d_dense2", "dh", "d_x1", "d_pre1", "d_dense1", "d_cx", "dqkv", "dx", "group_splits", "assign_mask")
+_BL_FWD_PLACE, _BL_BWD_PLACE = K.BL_FWD.placer(_BL_FWD_NAMES), K.BL_BWD.placer(_BL_BWD_NAMES)
+
+
+def _layer_consts(layer):
+    """What both paths of a fusion layer need of its parameters, cached on the layer per arena (arena views: fixed for the arena's life):
+    `params` (labelled _BL_PARAMS; also the parameter run of lav_bert_layer_rows_desc) and `bwd` (labelled _BL_BWD_CONSTS), the device addresses
+    of the parameters / the transposed copies and gradient accumulators, and the fused q | k | v views wqkv16, bqkv, gwqkv, gbqkv as tensors."""
+    arena = layer._arena()
+    c = layer.__dict__.get("_lav_stage_consts")
+    if c is not None and c[0] is arena:
+        return c[1]
+    att_m, ao, inter, outp = layer.attention.self, layer.attention.output, layer.intermediate, layer.output
+    Hd = att_m.query.weight.shape[1]
+    wqkv16, gwqkv, _ = arena.fused_view(att_m.query.weight, 3 * Hd)
+    _, gbqkv, bqkv = arena.fused_view(att_m.query.bias, 3 * Hd)
+    mats = (att_m.query.weight, ao.dense.weight, inter.dense.weight, outp.dense.weight)
+    params = (wqkv16, bqkv, W16(ao.dense.weight), ao.dense.bias.data, ao.LayerNorm.weight.data, ao.LayerNorm.bias.data, W16(inter.dense.weight),
+              inter.dense.bias.data, W16(outp.dense.weight), outp.dense.bias.data, outp.LayerNorm.weight.data, outp.LayerNorm.bias.data)
+    grads = [gwqkv, gbqkv] + [GR(p) for p in (ao.dense.weight, ao.dense.bias, ao.LayerNorm.weight, ao.LayerNorm.bias, inter.dense.weight,
+                                              inter.dense.bias, outp.dense.weight, outp.dense.bias, outp.LayerNorm.weight, outp.LayerNorm.bias)]
+    assert len(params) == len(_BL_PARAMS) and 2 * len(mats) + len(grads) == len(_BL_BWD_CONSTS)
+    return _stage_consts(layer, arena, params, [W16T(p) for p in mats], grads, eps=float(ao.LayerNorm.eps), eps2=float(outp.LayerNorm.eps),
+                         ffn=inter.dense.weight.shape[0], heads=layer.num_heads, wqkv16=wqkv16, bqkv=bqkv, gwqkv=gwqkv, gbqkv=gbqkv)
+
+
+def _bert_fwd_values(head, key_mask, resln_t, x, qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, y_ptr):
+    """lav_bert_layer_desc, labelled _BL_FWD_NAMES.  head: the scalars, seeds and parameter addresses; resln_t: (pre, mean, rstd, gamma, beta) of
+    the LayerNorm that produced x, or None; st1 / st2: the (2, R) statistics (mean, rstd) of the layer's two LayerNorms.  Called on the fresh
+    tensors (forward, eval) and on the unpacked saved ones (backward)."""
+    dp = K._dp
+    (mean1, rstd1), (mean2, rstd2) = _stat_rows(st1, 2), _stat_rows(st2, 2)
+    return head + (dp(key_mask), x.data_ptr()) + (tuple(t.data_ptr() for t in resln_t) if resln_t is not None else (0, 0, 0, 0, 0)) + (
+        qkv.data_ptr(), cx.data_ptr(), dp(lse), pre1.data_ptr(), mean1, rstd1, x1.data_ptr(), dp(h_pre), h.data_ptr(), pre2.data_ptr(), mean2, rstd2,
+        y_ptr)
+
+
 class BertLayerFn(torch.autograd.Function):
     """One post-LN BertLayer of the fusion encoder (HF BertLayer as called from model.py:242)."""
 
@@ -860,29 +909,24 @@ class BertLayerFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         rowmap = pair[0] if pair is not None else None
         assert pair is not None or x.shape[0] == R
-        f32 = torch.float32
         sdt = STREAM_DT if STREAM32 else bf16
         heads = layer.num_heads
-        arena = layer._arena()
-        att_m = layer.attention.self
-        wqkv16, _, _ = arena.fused_view(att_m.query.weight, 3 * Hd)
-        _, _, bqkv = arena.fused_view(att_m.query.bias, 3 * Hd)
+        c = _layer_consts(layer)
         keep = _keep(ctx)
-        resln_t = x32 if isinstance(x32, tuple) else None
+        resln_t = x32 if isinstance(x32, tuple) else None          # (pre, mean, rstd, gamma, beta) of the producing LayerNorm
         if STAGE_C and RESLN and _GQ == 1 and pair is None and (x32 is None or resln_t is not None):
-            return BertLayerFn._forward_c(ctx, x, resln_t, layer, key_mask, n, L, p_hidden, p_attn, want32, causal_from, keep, wqkv16, bqkv)
-        qkv = K.gemm(0, x, wqkv16, R, 3 * Hd, Hd, bias=bqkv, a_rowmap=rowmap)
+            return BertLayerFn._forward_c(ctx, x, resln_t, layer, c, key_mask, n, L, p_hidden, p_attn, want32, causal_from, keep)
+        qkv = K.gemm(0, x, c["wqkv16"], R, 3 * Hd, Hd, bias=c["bqkv"], a_rowmap=rowmap)
         s_att, s1, s2 = K.next_seed(), K.next_seed(), K.next_seed()
         att = K.Attn(1, heads, Hd // heads, n_seq=n, L=L, key_mask=key_mask, dropout_p=p_attn, seed=s_att, causal_from=int(causal_from))
         lse = torch.empty(att.lse_elems(), dtype=torch.float32, device=x.device) if keep else None
         cx = torch.empty((R, Hd), dtype=bf16, device=x.device)
         att.fwd(qkv, cx, lse)
         ao = layer.attention.output
-        resln_in = x32 if isinstance(x32, tuple) else None          # (pre, mean, rstd, gamma, beta) of the producing LayerNorm
         pre1 = K.gemm(0, cx, W16(ao.dense.weight), R, Hd, Hd, bias=ao.dense.bias.data, dropout_p=p_hidden, seed=s1,
-                      residual=(resln_in[0] if resln_in is not None else (x32 if x32 is not None else x)), res_rowmap=rowmap,
-                      res_ln=(resln_in[1:] if resln_in is not None else None), out_dtype=sdt)
-        x1_32 = torch.empty((R, Hd), dtype=f32, device=x.device) if (STREAM32 and not RESLN) else None
+                      residual=(resln_t[0] if resln_t is not None else (x32 if x32 is not None else x)), res_rowmap=rowmap,
+                      res_ln=(resln_t[1:] if resln_t is not None else None), out_dtype=sdt)
+        x1_32 = torch.empty((R, Hd), dtype=torch.float32, device=x.device) if (STREAM32 and not RESLN) else None
         x1, mean1, rstd1 = K.layernorm_fwd(pre1, R, Hd, ao.LayerNorm.weight.data, ao.LayerNorm.bias.data, ao.LayerNorm.eps,
                                            want_stats=keep or RESLN, out32=x1_32)
         inter, outp = layer.intermediate, layer.output
@@ -892,12 +936,12 @@ class BertLayerFn(torch.autograd.Function):
         pre2 = K.gemm(0, h, W16(outp.dense.weight), R, Hd, F, bias=outp.dense.bias.data, dropout_p=p_hidden, seed=s2,
                       residual=(pre1 if RESLN else (x1_32 if STREAM32 else x1)),
                       res_ln=((mean1, rstd1, ao.LayerNorm.weight.data, ao.LayerNorm.bias.data) if RESLN else None), out_dtype=sdt)
-        y32 = torch.empty((R, Hd), dtype=f32, device=x.device) if (STREAM32 and want32 and not RESLN) else None
+        y32 = torch.empty((R, Hd), dtype=torch.float32, device=x.device) if (STREAM32 and want32 and not RESLN) else None
         y, mean2, rstd2 = K.layernorm_fwd(pre2, R, Hd, outp.LayerNorm.weight.data, outp.LayerNorm.bias.data, outp.LayerNorm.eps,
                                           want_stats=keep or (RESLN and want32), out32=y32)
         if keep:
             ctx.layer, ctx.att, ctx.seeds, ctx.p = layer, att, (s1, s2), p_hidden
-            ctx.pair = pair
+            ctx.pair, ctx.c_consts = pair, c                  # c_consts: the FORWARD's constants (the cache may be rebuilt before the backward)
             ctx.save_for_backward(x, qkv, cx, lse, pre1, mean1, rstd1, x1, h_pre, h, pre2, mean2, rstd2)
         if RESLN and want32:
             ctx.mark_non_differentiable(pre2, mean2, rstd2)
@@ -906,76 +950,42 @@ class BertLayerFn(torch.autograd.Function):
         return y, y32
 
     @staticmethod
-    def _layer_consts(layer, arena, wqkv16, bqkv):
-        """device addresses of the layer's parameters / gradient accumulators / transposed copies (arena views: fixed for the arena's life)"""
-        c = layer.__dict__.get("_lav_stage_consts")
-        if c is not None and c[0] is arena:
-            return c[1]
-        att_m, ao, inter, outp = layer.attention.self, layer.attention.output, layer.intermediate, layer.output
-        Hd = wqkv16.shape[1]
-        _, gwqkv, _ = arena.fused_view(att_m.query.weight, 3 * Hd)
-        _, gbqkv, _ = arena.fused_view(att_m.query.bias, 3 * Hd)
-        dp = lambda t: t.data_ptr()
-        params = (dp(wqkv16), dp(bqkv), dp(W16(ao.dense.weight)), dp(ao.dense.bias.data), dp(ao.LayerNorm.weight.data), dp(ao.LayerNorm.bias.data),
-                  dp(W16(inter.dense.weight)), dp(inter.dense.bias.data), dp(W16(outp.dense.weight)), dp(outp.dense.bias.data),
-                  dp(outp.LayerNorm.weight.data), dp(outp.LayerNorm.bias.data))
-        wt = (W16T(att_m.query.weight), W16T(ao.dense.weight), W16T(inter.dense.weight), W16T(outp.dense.weight))
-        bwd = tuple(dp(t) for t in wt) + tuple(K._ld(t) for t in wt) + (
-            dp(gwqkv), dp(gbqkv), dp(GR(ao.dense.weight)), dp(GR(ao.dense.bias)), dp(GR(ao.LayerNorm.weight)), dp(GR(ao.LayerNorm.bias)),
-            dp(GR(inter.dense.weight)), dp(GR(inter.dense.bias)), dp(GR(outp.dense.weight)), dp(GR(outp.dense.bias)),
-            dp(GR(outp.LayerNorm.weight)), dp(GR(outp.LayerNorm.bias)))
-        consts = dict(params=params, bwd=bwd, eps=float(ao.LayerNorm.eps), eps2=float(outp.LayerNorm.eps), ffn=inter.dense.weight.shape[0], heads=layer.num_heads)
-        layer.__dict__["_lav_stage_consts"] = (arena, consts)
-        return consts
-
-    @staticmethod
     def _launch_c(x, resln_t, c, key_mask, n, L, p_hidden, p_attn, seeds, causal_from, keep):
-        """allocate one layer's activations and enqueue lav_bert_layer_fwd on them: (descriptor fields, (qkv, cx, lse, pre1, st1, x1, h_pre, h,
-        pre2, st2, y), residual addresses).  st1 / st2 = (mean, rstd) of the two LayerNorms; lse and h_pre exist only when `keep`."""
-        Hd, R = x.shape[1], n * L
-        dev, f32 = x.device, torch.float32
-        F = c["ffn"]
-        s_att = seeds[0]
-        e = torch.empty
+        """allocate one layer's activations and enqueue lav_bert_layer_fwd on them: (descriptor head, (qkv, cx, lse, pre1, st1, x1, h_pre, h,
+        pre2, st2, y)).  st1 / st2 = (mean, rstd) of the two LayerNorms; lse and h_pre exist only when `keep`."""
+        Hd, R, F = x.shape[1], n * L, c["ffn"]
+        dev, f32, e = x.device, torch.float32, torch.empty
         qkv, cx, x1, h, y = e((R, 3 * Hd), dtype=bf16, device=dev), e((R, Hd), dtype=bf16, device=dev), e((R, Hd), dtype=bf16, device=dev), \
             e((R, F), dtype=bf16, device=dev), e((R, Hd), dtype=bf16, device=dev)
         pre1, pre2 = e((R, Hd), dtype=STREAM_DT, device=dev), e((R, Hd), dtype=STREAM_DT, device=dev)
         st1, st2 = e((2, R), dtype=f32, device=dev), e((2, R), dtype=f32, device=dev)          # (mean, rstd) of the two LayerNorms
         lse = h_pre = None
         if keep:
-            att = K.Attn(1, c["heads"], Hd // c["heads"], n_seq=n, L=L, key_mask=key_mask, dropout_p=p_attn, seed=s_att, causal_from=int(causal_from))
+            att = K.Attn(1, c["heads"], Hd // c["heads"], n_seq=n, L=L, key_mask=key_mask, dropout_p=p_attn, seed=seeds[0], causal_from=int(causal_from))
             lse = e(att.lse_elems(), dtype=f32, device=dev)
             h_pre = e((R, F), dtype=bf16, device=dev)
-        if resln_t is not None:
-            res = tuple(t.data_ptr() for t in resln_t)         # (pre, mean, rstd, gamma, beta) of the producing LayerNorm
-        else:
-            res = (0, 0, 0, 0, 0)
-        p1, p2 = st1.data_ptr(), st2.data_ptr()
-        fields = (n, L, Hd, c["heads"], F, float(p_hidden), float(p_attn), c["eps"]) + tuple(seeds) + (int(causal_from),
-                  K._dp(key_mask)) + c["params"] + (x.data_ptr(),) + res + (
-                  qkv.data_ptr(), cx.data_ptr(), K._dp(lse), pre1.data_ptr(), p1, p1 + 4 * R, x1.data_ptr(), K._dp(h_pre), h.data_ptr(),
-                  pre2.data_ptr(), p2, p2 + 4 * R, y.data_ptr(), int(STREAM_DT == torch.float16), c["eps2"])
-        K.bert_layer_fwd(fields)
-        return fields, (qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, y), res
+        head = (n, L, Hd, c["heads"], F, float(p_hidden), float(p_attn), c["eps"]) + tuple(seeds) + (
+            int(causal_from), int(STREAM_DT == torch.float16), c["eps2"]) + c["params"]
+        K.bert_layer_fwd(_BL_FWD_PLACE(_bert_fwd_values(head, key_mask, resln_t, x, qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, y.data_ptr())))
+        return head, (qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, y)
 
     @staticmethod
-    def _forward_c(ctx, x, resln_t, layer, key_mask, n, L, p_hidden, p_attn, want32, causal_from, keep, wqkv16, bqkv):
+    def _forward_c(ctx, x, resln_t, layer, c, key_mask, n, L, p_hidden, p_attn, want32, causal_from, keep):
         """the same seven launches as the per-kernel path below, enqueued by ONE call of lav_bert_layer_fwd"""
         assert x.shape[0] == n * L and x.is_contiguous()
-        c = BertLayerFn._layer_consts(layer, layer._arena(), wqkv16, bqkv)
         s_att, s1, s2 = K.next_seed(), K.next_seed(), K.next_seed()
-        fields, (qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, y), res = BertLayerFn._launch_c(
+        head, (qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, y) = BertLayerFn._launch_c(
             x, resln_t, c, key_mask, n, L, p_hidden, p_attn, (s_att, s1, s2), causal_from, keep)
-        mean2, rstd2 = st2[0], st2[1]
         if keep:
-            ctx.layer, ctx.seeds, ctx.p = layer, (s1, s2), p_hidden
-            ctx.pair = None
-            # the backward rebuilds the activation addresses from the UNPACKED saved tensors (saved-tensor hooks may move them)
-            ctx.c_head, ctx.c_res, ctx.c_y, ctx.c_consts = fields[:12], res, y.data_ptr(), c
-            ctx.c_stage = True
+            ctx.layer, ctx.seeds, ctx.p, ctx.pair = layer, (s1, s2), p_hidden, None
+            # the backward rebuilds the activation addresses from the UNPACKED saved tensors (saved-tensor hooks may move them); kept from
+            # here: the descriptor head, gamma / beta of the residual carrier (parameters), the address of y (never read by the backward) and
+            # c_consts, the FORWARD's constants (not re-queried in the backward: the cache may have been rebuilt since)
+            ctx.c_stage, ctx.c_head, ctx.c_res_gb, ctx.c_y, ctx.c_consts = True, head, (resln_t[3:] if resln_t is not None else None), y.data_ptr(), c
             ctx.save_for_backward(x, qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, key_mask if key_mask is not None else x.new_empty(0),
                                   *(resln_t[:3] if resln_t is not None else ()))
         if want32:
+            mean2, rstd2 = st2[0], st2[1]
             ctx.mark_non_differentiable(pre2, mean2, rstd2)
             return y, pre2, mean2, rstd2
         return y, None
@@ -983,35 +993,20 @@ class BertLayerFn(torch.autograd.Function):
     @staticmethod
     def _backward_c(ctx, dy):
         layer = ctx.layer
-        x, qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2 = ctx.saved_tensors[:11]
-        R, Hd = cx.shape
-        c = ctx.c_consts                                       # the forward's constants (not re-queried: the cache may have been rebuilt since)
-        F = c["ffn"]
-        dev = x.device
-        e = torch.empty
+        x, qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, key_mask, *res = ctx.saved_tensors
+        key_mask = key_mask if key_mask.numel() else None
+        resln_t = tuple(res) + tuple(ctx.c_res_gb) if res else None
+        c, dev, e = ctx.c_consts, x.device, torch.empty
+        (R, Hd), F = cx.shape, c["ffn"]
         d_pre2, d_dense2, d_x1, d_pre1, d_dense1, d_cx, dx = (e((R, Hd), dtype=bf16, device=dev) for _ in range(7))
         dh, dqkv = e((R, F), dtype=bf16, device=dev), e((R, 3 * Hd), dtype=bf16, device=dev)
         splits = (K.splits_for(3 * Hd, Hd, R), K.splits_for(Hd, Hd, R), K.splits_for(F, Hd, R), K.splits_for(Hd, F, R))
-        b = c["bwd"]
         gs = K.group_splits_for(((Hd, F), (F, Hd), (Hd, Hd), (3 * Hd, Hd)), R)
-        saved = ctx.saved_tensors
-        key_mask = saved[11] if saved[11].numel() else None
-        res = ((saved[12].data_ptr(), saved[13].data_ptr(), saved[14].data_ptr()) + ctx.c_res[3:]) if len(saved) > 12 else ctx.c_res
-        p1, p2 = st1.data_ptr(), st2.data_ptr()
-        ffields = ctx.c_head + (K._dp(key_mask),) + c["params"] + (x.data_ptr(),) + res + (
-            qkv.data_ptr(), cx.data_ptr(), lse.data_ptr(), pre1.data_ptr(), p1, p1 + 4 * R, x1.data_ptr(), h_pre.data_ptr(), h.data_ptr(),
-            pre2.data_ptr(), p2, p2 + 4 * R, ctx.c_y, int(STREAM_DT == torch.float16), c["eps2"])
-        fields = ffields + (dy.data_ptr(),) + b[:20] + splits + (
-            d_pre2.data_ptr(), d_dense2.data_ptr(), dh.data_ptr(), d_x1.data_ptr(), d_pre1.data_ptr(), d_dense1.data_ptr(), d_cx.data_ptr(),
-            dqkv.data_ptr(), dx.data_ptr(), gs, _assign_mask((layer.output.dense.weight, layer.intermediate.dense.weight, layer.attention.output.dense.weight,
-                                                              layer.attention.self.query.weight)))
-        side = dw_stream(dev) if _DW_SIDE else None
-        _arm_join()
-        K.ensure_stage_workspaces(((3 * Hd, Hd), (Hd, Hd), (F, Hd), (Hd, F)), splits, gs, side.cuda_stream if side is not None else None)
-        K.bert_layer_bwd(fields, side.cuda_stream if side is not None else None)
-        if side is not None:                                   # operands of the weight-gradient GEMMs: not to be recycled before the side stream ran
-            for t in (d_dense2, h, dh, x1, d_dense1, cx, dqkv, x):
-                t.record_stream(side)
+        am = (layer.output.dense.weight, layer.intermediate.dense.weight, layer.attention.output.dense.weight, layer.attention.self.query.weight)
+        fwd = _bert_fwd_values(ctx.c_head, key_mask, resln_t, x, qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, ctx.c_y)
+        fields = _BL_BWD_PLACE(fwd + (dy.data_ptr(),) + c["bwd"] + splits + tuple(
+            t.data_ptr() for t in (d_pre2, d_dense2, dh, d_x1, d_pre1, d_dense1, d_cx, dqkv, dx)) + (gs, _assign_mask(am)))     # labelled _BL_BWD_NAMES
+        _stage_bwd(K.bert_layer_bwd, fields, ((3 * Hd, Hd), (Hd, Hd), (F, Hd), (Hd, F)), splits, gs, dev, (d_dense2, h, dh, x1, d_dense1, cx, dqkv, x))
         return None, dx, None, None, None, None, None, None, None, None, None, None
 
     @staticmethod
@@ -1023,11 +1018,8 @@ class BertLayerFn(torch.autograd.Function):
         layer, att, (s1, s2), p = ctx.layer, ctx.att, ctx.seeds, ctx.p
         x, qkv, cx, lse, pre1, mean1, rstd1, x1, h_pre, h, pre2, mean2, rstd2 = ctx.saved_tensors
         R, Hd = cx.shape
-        arena = layer._arena()
         att_m, ao, inter, outp = layer.attention.self, layer.attention.output, layer.intermediate, layer.output
         F = inter.dense.weight.shape[0]
-        wqkv16, gwqkv, _ = arena.fused_view(att_m.query.weight, 3 * Hd)
-        _, gbqkv, _ = arena.fused_view(att_m.query.bias, 3 * Hd)
         dy = dy.contiguous()
         # out = LN(pre2), pre2 = x1 + dropout(dense(h))
         d_dense2 = torch.empty((R, Hd), dtype=bf16, device=x.device)
@@ -1047,31 +1039,27 @@ class BertLayerFn(torch.autograd.Function):
         d_cx = K.gemm(0, d_dense1, W16T(ao.dense.weight), R, Hd, Hd)
         dqkv = torch.empty_like(qkv)
         att.bwd(qkv, cx, d_cx, lse, dqkv, None)
+        rows = x.shape[0]                                  # R, or with a pair map the U un-expanded source rows
         if ctx.pair is not None:
             # every pair row that read source row u sends its gradient back to u: sum the pair rows first (one gather-sum each
             # for dqkv and the residual branch), then the weight gradient and the input gradient run on the U source rows
             _, start, order = ctx.pair
-            U = x.shape[0]
-            dqkv_u = K.gather_sum_rows(dqkv, start, order, U, 3 * Hd)
-            d_pre1_u = K.gather_sum_rows(d_pre1, start, order, U, Hd)
-            grp.add(dqkv_u, x, 3 * Hd, Hd, U, (gwqkv, GW(att_m.query.weight)[1]), K.splits_for(3 * Hd, Hd, U), rowsum_a=gbqkv)
-            grp.launch(x.device)
-            dx = K.gemm(0, dqkv_u, W16T(att_m.query.weight), U, Hd, 3 * Hd, residual=d_pre1_u)
-            return None, dx, None, None, None, None, None, None, None, None, None, None
-        grp.add(dqkv, x, 3 * Hd, Hd, R, (gwqkv, GW(att_m.query.weight)[1]), K.splits_for(3 * Hd, Hd, R), rowsum_a=gbqkv)
+            dqkv = K.gather_sum_rows(dqkv, start, order, rows, 3 * Hd)
+            d_pre1 = K.gather_sum_rows(d_pre1, start, order, rows, Hd)
+        c = ctx.c_consts
+        grp.add(dqkv, x, 3 * Hd, Hd, rows, (c["gwqkv"], GW(att_m.query.weight)[1]), K.splits_for(3 * Hd, Hd, rows), rowsum_a=c["gbqkv"])
         grp.launch(x.device)
-        dx = K.gemm(0, dqkv, W16T(att_m.query.weight), R, Hd, 3 * Hd, residual=d_pre1)
+        dx = K.gemm(0, dqkv, W16T(att_m.query.weight), rows, Hd, 3 * Hd, residual=d_pre1)
         return None, dx, None, None, None, None, None, None, None, None, None, None
 
 
-def bert_layer_eval_c(x, resln_t, layer, c, key_mask, n, L):
+def bert_layer_eval_c(x, resln_t, layer, key_mask, n, L):
     """BertLayerFn._forward_c at eval (no dropout, nothing kept, causal_from 0, no seeds drawn), returning the layer's qkv too:
     (y, (pre2, mean2, rstd2, gamma2, beta2) for the next layer's residual, qkv).  The prefix pass of caption decoding (caption_decode.py)."""
     assert x.shape[0] == n * L and x.is_contiguous()
-    _, (qkv, _, _, _, _, _, _, _, pre2, st2, y), _ = BertLayerFn._launch_c(x, resln_t, c, key_mask, n, L, 0.0, 0.0, (0, 0, 0), 0, False)
+    _, (qkv, _, _, _, _, _, _, _, pre2, st2, y) = BertLayerFn._launch_c(x, resln_t, _layer_consts(layer), key_mask, n, L, 0.0, 0.0, (0, 0, 0), 0, False)
     out = layer.output.LayerNorm
     return y, (pre2, st2[0], st2[1], out.weight.data, out.bias.data), qkv
-
 
 
 def bert_layer_rows_eval(x, x32, layer, key_mask, n, L, q_row, res_rowmap, x_rowmap=None):
@@ -1079,32 +1067,26 @@ def bert_layer_rows_eval(x, x32, layer, key_mask, n, L, q_row, res_rowmap, x_row
     GEMM on row q_row[s] of every sequence s.  x / x32 are what model._encode hands the layer: x the bf16 input (n * L rows, or the un-expanded
     pair source read through x_rowmap), x32 None (residual = x), an fp32 tensor, or RESLN's (pre, mean, rstd, gamma, beta).  res_rowmap (n,)
     int32: the residual row of each selected row.  Returns (y bf16, y32 fp32), both (n, H)."""
-    Hd, dev, f32 = x.shape[1], x.device, torch.float32
-    arena = layer._arena()
-    att_m, ao, inter, outp = layer.attention.self, layer.attention.output, layer.intermediate, layer.output
-    wqkv16, _, _ = arena.fused_view(att_m.query.weight, 3 * Hd)
-    _, _, bqkv = arena.fused_view(att_m.query.bias, 3 * Hd)
-    F = inter.dense.weight.shape[0]
+    Hd, dev, f32, e, dp = x.shape[1], x.device, torch.float32, torch.empty, K._dp
+    c = _layer_consts(layer)
+    F = c["ffn"]
     if isinstance(x32, tuple):
         res, (rm, rr, rg, rb) = x32[0], x32[1:]
     else:
         res, rm, rr, rg, rb = (x32 if x32 is not None else x), None, None, None, None
     res_dtype = {bf16: 0, f32: 1, torch.float16: 2}[res.dtype]
-    e = torch.empty
     qkv = e((n * L, 3 * Hd), dtype=bf16, device=dev)
     cx, x1, y = (e((n, Hd), dtype=bf16, device=dev) for _ in range(3))
     pre1, pre2, y32 = (e((n, Hd), dtype=f32, device=dev) for _ in range(3))
     st = e((4, n), dtype=f32, device=dev)
     h = e((n, F), dtype=bf16, device=dev)
-    dp = K._dp
-    d = K.L.BertLayerRowsDesc(n, L, Hd, layer.num_heads, F, float(ao.LayerNorm.eps), float(outp.LayerNorm.eps), dp(key_mask), dp(q_row),
-                              dp(wqkv16), dp(bqkv), dp(W16(ao.dense.weight)), dp(ao.dense.bias.data), dp(ao.LayerNorm.weight.data),
-                              dp(ao.LayerNorm.bias.data), dp(W16(inter.dense.weight)), dp(inter.dense.bias.data), dp(W16(outp.dense.weight)),
-                              dp(outp.dense.bias.data), dp(outp.LayerNorm.weight.data), dp(outp.LayerNorm.bias.data), dp(x), dp(x_rowmap), dp(res),
+    # lav_bert_layer_rows_desc declares the twelve parameter addresses in the order of _BL_PARAMS
+    d = K.L.BertLayerRowsDesc(n, L, Hd, c["heads"], F, c["eps"], c["eps2"], dp(key_mask), dp(q_row), *c["params"], dp(x), dp(x_rowmap), dp(res),
                               K._ld(res), res_dtype, dp(res_rowmap), dp(rm), dp(rr), dp(rg), dp(rb), dp(qkv), dp(cx), dp(pre1), dp(st[0]), dp(st[1]),
                               dp(x1), dp(h), dp(pre2), dp(st[2]), dp(st[3]), dp(y), dp(y32))
     K.bert_layer_fwd_rows(d)
     return y, y32
+
 
 class MLMHeadFn(torch.autograd.Function):
     """BertOnlyMLMHead (main_pretrain_mlm.py:46-48,69,115): dense+GELU, LayerNorm, vocab projection."""

@@ -101,6 +101,7 @@ def _ld(t):
 
 
 import struct as _struct
+from operator import itemgetter as _itemgetter
 import threading as _threading
 import os as _os_mod
 _os_env = _os_mod.environ.get
@@ -185,66 +186,82 @@ def gemm_tn_grouped(jobs, splits):
         L.check(rc, "lav_gemm_tn_grouped")
 
 
-# ---- stage-level entries (lavender_amd/csrc/stages.cpp): one C call per fusion-encoder layer pass ------------------------------------
-_BL_FWD_PACK = _struct.Struct("@5i3f3Ii32Pif")
-_BL_BWD_PACK = _struct.Struct("@5i3f3Ii32Pif5P4q12P4i9Pii")
-assert _BL_FWD_PACK.size == C.sizeof(L.BertLayerDesc) and _BL_BWD_PACK.size == C.sizeof(L.BertLayerBwdDesc)
+# ---- stage-level entries (lavender_amd/csrc/stages.cpp): one C call per Swin block / fusion-encoder layer pass ----------------------------
+_PACK_CODE = {L.i32: "i", L.f32: "f", L.u32: "I", L.i64: "q", L.vp: "P"}
 
 
-def _stage_buffers():
-    b = getattr(_tls, "stage", None)
-    if b is None:
-        rf, rb = C.create_string_buffer(C.sizeof(L.BertLayerDesc)), C.create_string_buffer(C.sizeof(L.BertLayerBwdDesc))
-        b = _tls.stage = (rf, C.cast(rf, C.POINTER(L.BertLayerDesc)), rb, C.cast(rb, C.POINTER(L.BertLayerBwdDesc)))
-    return b
+class DescLayout:
+    """Flat view of a ctypes descriptor declaration (nested structs flattened): .names in declaration order, .pos name -> position and .pack,
+    the struct.Struct that fills the descriptor with ONE pack_into (native alignment "@" reproduces the C layout)."""
+
+    def __init__(self, st):
+        self.struct = st
+        fields, fmt = self._flatten(st)
+        self.names = tuple(n for n, _ in fields)
+        self.pos = {n: i for i, n in enumerate(self.names)}
+        assert len(self.pos) == len(self.names), "field names of a descriptor and its nested parts must be distinct"
+        self.pack = _struct.Struct("@" + fmt)
+        self._tls = _threading.local()
+        assert self.pack.size <= C.sizeof(st) < self.pack.size + 8, st          # only tail padding may differ
+
+    @staticmethod
+    def _flatten(st):
+        fields, fmt = [], ""
+        for name, ct in st._fields_:
+            if issubclass(ct, C.Structure):
+                sub, f = DescLayout._flatten(ct)
+                fields += sub
+                fmt += f + {4: "0i", 8: "0q"}[C.alignment(ct)]                    # the nested struct's own tail padding
+            else:
+                fields.append((name, ct))
+                fmt += _PACK_CODE[ct]
+        return fields, fmt
+
+    def fill(self, fields):
+        """this thread's descriptor filled with one pack_into: the pointer to hand the C entry"""
+        b = getattr(self._tls, "b", None)
+        if b is None:
+            raw = C.create_string_buffer(C.sizeof(self.struct))
+            b = self._tls.b = (raw, C.cast(raw, C.POINTER(self.struct)))
+        self.pack.pack_into(b[0], 0, *fields)
+        return b[1]
+
+    def placer(self, names, partial=False):
+        """f(values given in the order of `names`) -> the values in declaration order.  The permutation is worked out here, once; a call
+        is one itemgetter.  partial: fields that `names` lacks are filled with 0 (otherwise they are an error)."""
+        src = {n: i for i, n in enumerate(names)}
+        assert len(src) == len(names) and not set(names) - set(self.names), (set(names) - set(self.names), len(src), len(names))
+        assert partial or len(names) == len(self.names), set(self.names) - set(names)
+        pick = _itemgetter(*(src.get(n, len(names)) for n in self.names))
+        return (lambda vals: pick(vals + (0,))) if len(names) != len(self.names) else pick
 
 
-_SB_FWD_PACK = _struct.Struct("@5if29P")
-_SB_BWD_PACK = _struct.Struct("@5if29PP2f4P4q13P4i7Pii")
-assert _SB_FWD_PACK.size == C.sizeof(L.SwinBlockDesc) and _SB_BWD_PACK.size == C.sizeof(L.SwinBlockBwdDesc)
+BL_FWD, BL_BWD, SB_FWD, SB_BWD = (DescLayout(st) for st in (L.BertLayerDesc, L.BertLayerBwdDesc, L.SwinBlockDesc, L.SwinBlockBwdDesc))
+_BL_FWD_PACK, _BL_BWD_PACK, _SB_FWD_PACK, _SB_BWD_PACK = BL_FWD.pack, BL_BWD.pack, SB_FWD.pack, SB_BWD.pack
 
 
-def _swin_buffers():
-    b = getattr(_tls, "swin", None)
-    if b is None:
-        rf, rb = C.create_string_buffer(C.sizeof(L.SwinBlockDesc)), C.create_string_buffer(C.sizeof(L.SwinBlockBwdDesc))
-        b = _tls.swin = (rf, C.cast(rf, C.POINTER(L.SwinBlockDesc)), rb, C.cast(rb, C.POINTER(L.SwinBlockBwdDesc)))
-    return b
+def _stage_call(name, layout, fields, *streams):
+    rc = getattr(L.lib, name)(_s(), *streams, layout.fill(fields))
+    if rc != 0:
+        L.check(rc, name)
 
 
 def swin_block_fwd(fields):
-    """fields: lav_swin_block_desc in declaration order (field 7 = address of the window lav_attn_desc)."""
-    rf, pf, _, _ = _swin_buffers()
-    _SB_FWD_PACK.pack_into(rf, 0, *fields)
-    rc = L.lib.lav_swin_block_fwd(_s(), pf)
-    if rc != 0:
-        L.check(rc, "lav_swin_block_fwd")
+    """fields: lav_swin_block_desc in declaration order (SB_FWD.names: ints / floats / device addresses, 0 = NULL)"""
+    _stage_call("lav_swin_block_fwd", SB_FWD, fields)
 
 
 def swin_block_bwd(fields, side_stream):
-    _, _, rb, pb = _swin_buffers()
-    _SB_BWD_PACK.pack_into(rb, 0, *fields)
-    rc = L.lib.lav_swin_block_bwd(_s(), side_stream, pb)
-    if rc != 0:
-        L.check(rc, "lav_swin_block_bwd")
+    _stage_call("lav_swin_block_bwd", SB_BWD, fields, side_stream)
 
 
 def bert_layer_fwd(fields):
-    """fields: the 46 values of lav_bert_layer_desc in declaration order (ints / floats / device addresses, 0 = NULL)."""
-    rf, pf, _, _ = _stage_buffers()
-    _BL_FWD_PACK.pack_into(rf, 0, *fields)
-    rc = L.lib.lav_bert_layer_fwd(_s(), pf)
-    if rc != 0:
-        L.check(rc, "lav_bert_layer_fwd")
+    _stage_call("lav_bert_layer_fwd", BL_FWD, fields)
 
 
 def bert_layer_bwd(fields, side_stream):
-    """fields: lav_bert_layer_bwd_desc in declaration order (the forward's 46 values first); side_stream: raw hipStream_t or None."""
-    _, _, rb, pb = _stage_buffers()
-    _BL_BWD_PACK.pack_into(rb, 0, *fields)
-    rc = L.lib.lav_bert_layer_bwd(_s(), side_stream, pb)
-    if rc != 0:
-        L.check(rc, "lav_bert_layer_bwd")
+    """fields: lav_bert_layer_bwd_desc in declaration order (BL_BWD.names: the forward's values first); side_stream: raw hipStream_t or None"""
+    _stage_call("lav_bert_layer_bwd", BL_BWD, fields, side_stream)
 
 
 import os as _os
