@@ -4,7 +4,7 @@
  * point below replaces the device work that a reference torch op sequence does; the reference
  * file:line it stands in for is cited per function (paths relative to the reference root).
  *
- * Conventions, as the code really behaves (ABI 6):
+ * Conventions, as the code really behaves (ABI 7):
  *   - C linkage, POD arguments, no torch types.  Every function returns 0 on success or a negative
  *     LAV_E_* code (-1 argument, -2 launch, -3 unsupported, -4 workspace); lav_last_error() returns a message for the calling
  *     thread.  Nothing throws/exits.
@@ -145,7 +145,8 @@ int lav_gemm_tn_grouped(void* stream, int n_jobs, const lav_gemm_tn_job* jobs, i
 /* Tuning / probe hook: selects between kernel variants at run time (within-process A/B measurements in tools/): which 2 = ping-pong
  * weight-gradient kernel on/off, 5 = probe bits of the 256x256 kernel (timing only, wrong results), 6 = column-group width of the tile
  * walk, 7 / 9 = 192-row tiles / their loader-wave form on/off, 11 = phase-shifted two-group tile (bit 0: 256-row, bit 1: 192-row;
- * results bit-identical to the tiles it replaces), 12 = fewest output rows for the 256-row weight-gradient tiles (LAV_GEMM_TN_MINM).  Returns the
+ * results bit-identical to the tiles it replaces), 12 = fewest output rows for the 256-row weight-gradient tiles (LAV_GEMM_TN_MINM), 13 = grouped
+ * weight-gradient launches on/off (LAV_GEMM_TN_GROUP).  2, 12 and 13 also move the split factors lav_gemm_splits / lav_gemm_tn_splits answer with.  Returns the
  * previous value, -1 for an unknown selector.  Results are identical up to fp32 summation order (except selector 5). */
 int lav_gemm_select(int which, int value);
 /* Probe hooks, not part of the contract: the launches lav_gemm_bf16 / lav_gemm_tn_grouped would make for a call, in order, without making them (no
@@ -160,6 +161,18 @@ typedef struct lav_gemm_launch_info {
 int lav_gemm_plan(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits,
                   lav_gemm_launch_info* out, int max_out);
 int lav_gemm_tn_grouped_plan(int n_jobs, const lav_gemm_tn_job* jobs, int splits, lav_gemm_launch_info* out, int max_out);
+/* Split-K policy (additive in ABI 7; no device is needed).  Scratch is caller-owned, so the caller has to know a call's split factor and workspace
+ * bytes BEFORE the call: these two entries answer both from the route plan the call itself will take.
+ * lav_gemm_splits: arguments as lav_gemm_plan.  splits <= 0 asks for the library's own factor -- layout 2: a weight gradient on the tile the plan gives it
+ * (epi->k_keep only tested for presence); layouts 0 / 1: a long-K product without epilogue whose output under-fills the machine, else 1 -- and splits > 0
+ * keeps the caller's.  Returns that factor (>= 1), or the error code lav_gemm_bf16 would return.  With ws_bytes != NULL the call is validated as by
+ * lav_gemm_bf16 and *ws_bytes receives the LAV_WS_SPLITK bytes it will request (0: none); with NULL only the factor is worked out (epi may be NULL then).
+ * lav_gemm_tn_splits: jobs as for lav_gemm_tn_grouped_plan (up to four weight gradients of one stage, a common contraction).  A job whose fallback_splits
+ * is <= 0 has it REPLACED by the library's factor for that job alone.  Returns the group factor to hand lav_gemm_tn_grouped (splits > 0: the caller's;
+ * else the library's), 0 when that entry would run the jobs one by one, or a negative error code.  *ws_bytes (may be NULL) receives the LAV_WS_SPLITK
+ * bytes that cover the grouped launch AND each job run alone with its fallback_splits (the stage entries do the latter without a second stream). */
+int lav_gemm_splits(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits, size_t* ws_bytes);
+int lav_gemm_tn_splits(int n_jobs, lav_gemm_tn_job* jobs, int splits, size_t* ws_bytes);
 /* Same kind of hook for the large-window attention kernels (windows of up to 768 tokens without the precomputed tables, attention_winl.hip): parts = 0
  * lets the library split a problem into query parts by its own rule (the default), 1 / 3 force that many, -1 routes large windows to the generic
  * kernels (tests compare the two).  Process-wide; returns the previous value. */
@@ -807,7 +820,8 @@ int lav_answer_readout(void* stream, int n, int V, const void* logits, long ld, 
  * choice on one box.
  *   LAV_GEMM_TN_KIND (0 / 1: weight-gradient tiles of at most 128x128 / 256x128), LAV_GEMM_PP_TN (0: no ping-pong 256x256
  *   weight-gradient kernel), LAV_GEMM_TN_MINM (fewest output rows for the 256-row weight-gradient tiles, default 160),
- *   LAV_GEMM_TN_GROUP (0: grouped weight-gradient launches run job by job), LAV_GEMM_GROUP_N (column-group width of the 256x256 tile
+ *   LAV_GEMM_TN_GROUP (0: grouped weight-gradient launches run job by job), LAV_TN_BLOCKS / LAV_TN_GROUP_BLOCKS / LAV_TN_GROUP_BLOCKS_WIDE (workgroups the
+ *   split-K policy aims one weight-gradient GEMM / a grouped launch / a grouped launch of >= 96 tiles at: 128 / 192 / as the one before), LAV_GEMM_GROUP_N (column-group width of the 256x256 tile
  *   walk), LAV_GEMM_H192 / LAV_GEMM_H192L (0: no 192-row tiles / no loader waves), LAV_GEMM_PS (bit 0 / bit 1: phase-shifted two-group form of
  *   the 256-row / 192-row tile, default 3), LAV_NT_STORES (read twice, with different defaults: by the GEMM epilogue, default 5 -- bit 0: GELU'
  *   stored non-temporally, bit 2: loaded non-temporally; by lav_adamw_step, default 1 -- bit 1: non-temporal parameter / moment
@@ -815,8 +829,8 @@ int lav_answer_readout(void* stream, int n, int V, const void* logits, long ld, 
  *   LAV_LN_ATOMIC_FLUSH (LayerNorm backward column sums by per-block atomics), LAV_LN_G32 (bit 0 / bit 1: 32-lane x 3-chunk rows for C = 768 in the
  *   forward / backward, default 1), LAV_WINL / LAV_SEQL (0: large windows / long sequences on the generic kernels).
  * lav_gemm_select(which, value) changes these GEMM ones at run time (same caveat: process-wide, for probes): 2 = LAV_GEMM_PP_TN, 5 = LAV_GEMM_DBG,
- * 6 = LAV_GEMM_GROUP_N, 7 = LAV_GEMM_H192, 9 = LAV_GEMM_H192L, 11 = LAV_GEMM_PS, 12 = LAV_GEMM_TN_MINM; the others (LAV_GEMM_TN_KIND,
- * LAV_GEMM_TN_GROUP, LAV_NT_STORES) are fixed when the library is loaded.
+ * 6 = LAV_GEMM_GROUP_N, 7 = LAV_GEMM_H192, 9 = LAV_GEMM_H192L, 11 = LAV_GEMM_PS, 12 = LAV_GEMM_TN_MINM, 13 = LAV_GEMM_TN_GROUP; the others (LAV_GEMM_TN_KIND,
+ * LAV_TN_BLOCKS, LAV_TN_GROUP_BLOCKS, LAV_TN_GROUP_BLOCKS_WIDE, LAV_NT_STORES) are fixed when the library is loaded.
  * lav_probe_win_prof(buf): NULL = off; else the next stage-2-sized window backward runs the s_memtime-stamped build of win_bwd1 and
  * writes 160 uint64 stamps to the device buffer `buf` (tools/win_prof.py; profiles/r05_win_bwd1.md).
  * --------------------------------------------------------------------------------------------- */

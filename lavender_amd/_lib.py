@@ -161,6 +161,8 @@ _SIGS = {
     "lav_gemm_tn_grouped": (i32, [vp, i32, P(GemmTnJob), i32]),
     "lav_gemm_plan": (i32, [i32, i32, i32, i32, i64, i64, i64, P(GemmEpilogue), i32, P(GemmLaunchInfo), i32]),
     "lav_gemm_tn_grouped_plan": (i32, [i32, P(GemmTnJob), i32, P(GemmLaunchInfo), i32]),
+    "lav_gemm_splits": (i32, [i32, i32, i32, i32, i64, i64, i64, P(GemmEpilogue), i32, P(C.c_size_t)]),
+    "lav_gemm_tn_splits": (i32, [i32, P(GemmTnJob), i32, P(C.c_size_t)]),
     "lav_bert_layer_fwd": (i32, [vp, P(BertLayerDesc)]),
     "lav_bert_layer_bwd": (i32, [vp, vp, P(BertLayerBwdDesc)]),
     "lav_swin_block_fwd": (i32, [vp, P(SwinBlockDesc)]),

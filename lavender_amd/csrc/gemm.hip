@@ -12,6 +12,7 @@
 #include "common.h"
 #include <type_traits>
 #include <stdlib.h>
+#include <math.h>
 #include "../../include/lavender_hip.h"
 
 #define BM 128
@@ -1669,20 +1670,26 @@ struct GemmSwitches {
     int ps;          // LAV_GEMM_PS (select 11): phase-shifted kernel instead of gemm_huge (bit 0) / gemm_h192l (bit 1) for the specialised layout-0 epilogues (round 6: -2.0 ms per cfg2 step)
     int tn_min_m;    // LAV_GEMM_TN_MINM (select 12): fewest output rows that take the 256-row weight-gradient tiles (outputs with 160 ... 255 rows, Swin-L stage 0: C = 192,
                      // leave a quarter of the tile idle and are still well ahead of the 128 x 128 kernel; 256 restores the old threshold)
-    int tn_group;    // LAV_GEMM_TN_GROUP: 0 = lav_gemm_tn_grouped runs its jobs one by one
+    int tn_group;    // LAV_GEMM_TN_GROUP (select 13): 0 = lav_gemm_tn_grouped runs its jobs one by one
     int nt_stores;   // LAV_NT_STORES: 1: GELU' stored non-temporally, 4: and loaded non-temporally by the gradient epilogue (73.30 -> 73.12 ms per step, two interleaved pairs)
+    // workgroups the split-K policy aims a weight-gradient launch at (tn_splits / tn_group_splits; sweeps: profiles/r04_gemm_experiments.md section 8,
+    // profiles/r04_late_experiments.md section 11)
+    int tn_blocks;               // LAV_TN_BLOCKS: one weight-gradient GEMM on the large tiles
+    int tn_group_blocks;         // LAV_TN_GROUP_BLOCKS: a grouped launch
+    int tn_group_blocks_wide;    // LAV_TN_GROUP_BLOCKS_WIDE: a grouped launch of >= 96 tiles (the fusion layers); default = tn_group_blocks
 };
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 static GemmSwitches gemm_sw = {env_int("LAV_GEMM_TN_KIND", -1), env_int("LAV_GEMM_PP_TN", 1) != 0, env_int("LAV_GEMM_DBG", 0), env_int("LAV_GEMM_GROUP_N", -1),
                                env_int("LAV_GEMM_H192", 1), env_int("LAV_GEMM_H192L", 1), env_int("LAV_GEMM_PS", 3), env_int("LAV_GEMM_TN_MINM", 160),
-                               env_int("LAV_GEMM_TN_GROUP", 1) != 0, env_int("LAV_NT_STORES", 5)};
-// probe hook (within-process A/B): which = 2 pp_tn, 5 dbg, 6 group_n, 7 h192, 9 h192l, 11 ps, 12 tn_min_m; returns the old value, -1 for an unknown id
+                               env_int("LAV_GEMM_TN_GROUP", 1) != 0, env_int("LAV_NT_STORES", 5), env_int("LAV_TN_BLOCKS", 128),
+                               env_int("LAV_TN_GROUP_BLOCKS", 192), env_int("LAV_TN_GROUP_BLOCKS_WIDE", env_int("LAV_TN_GROUP_BLOCKS", 192))};
+// probe hook (within-process A/B): which = 2 pp_tn, 5 dbg, 6 group_n, 7 h192, 9 h192l, 11 ps, 12 tn_min_m, 13 tn_group; returns the old value, -1 for an unknown id
 extern "C" int lav_gemm_select(int which, int value) {
     int* const p = which == 2 ? &gemm_sw.pp_tn : which == 5 ? &gemm_sw.dbg : which == 6 ? &gemm_sw.group_n : which == 7 ? &gemm_sw.h192 :
-                   which == 9 ? &gemm_sw.h192l : which == 11 ? &gemm_sw.ps : which == 12 ? &gemm_sw.tn_min_m : nullptr;
+                   which == 9 ? &gemm_sw.h192l : which == 11 ? &gemm_sw.ps : which == 12 ? &gemm_sw.tn_min_m : which == 13 ? &gemm_sw.tn_group : nullptr;
     if (!p) return -1;
     const int old = *p;
-    *p = which == 2 ? value != 0 : value;
+    *p = which == 2 || which == 13 ? value != 0 : value;
     return old;
 }
 
@@ -1781,6 +1788,18 @@ static bool tn_pp_fits(int M, int N, int K, const void* k_keep, int k_rows_per_g
     return sw.pp_tn && sw.tn_kind != 0 && sw.tn_kind != 1 && tn_rows_enough(M, N, sw) && (N % 256) == 0 && (K % PP_BK) == 0 &&
            (!k_keep || (k_rows_per_group >= keep_rows && (K + k_rows_per_group - 1) / k_rows_per_group <= 128));
 }
+// the weight-gradient tile of a plain flush over contraction K: 0 = 128 x 128 (two-group kernel), 1 = 256 x 128, 2 = 256 x 256
+static int tn_tile_kind(int M, int N, int K, const void* k_keep, int k_rows_per_group, const GemmSwitches& sw) {
+    if ((K % BKT) == 0 && tn_rows_enough(M, N, sw) && (!k_keep || k_rows_per_group >= BKT))
+        return sw.tn_kind == 0 ? 0 : (N % 256) == 0 && sw.tn_kind != 1 ? 2 : 1;
+    // contraction lengths that are multiples of 32 but not of 64 (Swin stage 3: 7840 token rows): the ping-pong kernel walks k-tiles of 32
+    // (k_per_split is a multiple of 64, so only the last split ends on a 32-boundary) -- before round 4 these fell to the 128 x 128 kernel
+    return (K % BKT) != 0 && tn_pp_fits(M, N, K, k_keep, k_rows_per_group, BKT, sw) ? 2 : 0;
+}
+// a long weight-gradient contraction without drop-path rows on an output with rows enough: a K that is no multiple of the k-tile is split off (gemm_plan)
+static bool tn_long_k(int M, int N, int K, bool keep, const GemmSwitches& sw) { return !keep && tn_rows_enough(M, N, sw) && K >= 2048 && sw.tn_kind != 0; }
+// a workspace split-K of layouts 0 / 1 on the 256 x 256 tiles
+static bool nn_sk_huge(int M, int N, int K) { return (K % BKT) == 0 && M >= BIG_BM && (N % 256) == 0; }
 static int gemm_group_n(int N, const GemmSwitches& sw) {
     const int tn = N / 256;
     return sw.group_n >= 0 ? sw.group_n : (tn >= 8 && tn % 4 == 0 ? 4 : 0);
@@ -1844,7 +1863,7 @@ static GemmPlanError gemm_plan_part(GemmPart& q, int layout, int M, int N, int k
     }
     if (layout != 2) {
         const bool sk = splits > 1 && e.out_mode == 0;       // under-filled long-K problem (vocabulary contraction): workspace split-K
-        const bool sk_huge = sk && (K % BKT) == 0 && M >= 256 && (N % 256) == 0;
+        const bool sk_huge = sk && nn_sk_huge(M, N, K);
         q.group_n = 0; q.dbg = 0;
         if (sk_huge) q.gemm = {GK_HUGE + 2 * FI_ALL + layout, (unsigned)(t_huge * splits), 256, 256};
         else q.gemm = {GK_SMALL + layout, (unsigned)(t_small * splits), 128, 128};
@@ -1860,12 +1879,7 @@ static GemmPlanError gemm_plan_part(GemmPart& q, int layout, int M, int N, int k
     // flush (out_mode 2): one block per output tile -> plain read-modify-write; split-K -> private partial tiles in a
     // workspace + one reduction pass.  fp32 atomics only remain for ragged N.
     const bool plain = tn_plain(e);
-    int kind = 0;                                            // 0: 128x128 two-group kernel, 1: 256x128, 2: 256x256
-    const bool large_ok = plain && (K % BKT) == 0 && tn_rows_enough(M, N, sw) && (!e.k_keep || e.k_rows_per_group >= BKT);
-    if (large_ok && sw.tn_kind != 0) kind = (N % 256) == 0 && sw.tn_kind != 1 ? 2 : 1;
-    // contraction lengths that are multiples of 32 but not of 64 (Swin stage 3: 7840 token rows): the ping-pong kernel walks k-tiles of 32
-    // (k_per_split is a multiple of 64, so only the last split ends on a 32-boundary) -- before round 4 these fell to the 128 x 128 kernel
-    if (!large_ok && plain && (K % BKT) != 0 && tn_pp_fits(M, N, K, e.k_keep, e.k_rows_per_group, BKT, sw)) kind = 2;
+    const int kind = plain ? tn_tile_kind(M, N, K, e.k_keep, e.k_rows_per_group, sw) : 0;
     q.group_n = 0; q.dbg = 0;
     q.rpt = kind ? BIG_BM : BM;
     const int ws_tiles = ((M + q.rpt - 1) / q.rpt) * ((N + BN - 1) / BN);
@@ -1893,7 +1907,7 @@ static GemmPlan gemm_plan(int layout, int M, int N, int K, long lda, long ldb, l
     // weight-gradient stream).  Split it instead: the first K - K % 64 rows on the large-tile kernels (with the call's split factor, clamped to what
     // the whole K allows), the < 64-row tail on the small one; both accumulate into C on the same stream (alpha, rowsum_a apply to both parts);
     // the first part assigns when the call does, the tail always accumulates.
-    if (layout == 2 && tn_plain(e) && !e.k_keep && tn_rows_enough(M, N, sw) && K >= 2048 && (K % PP_BK) != 0 && sw.tn_kind != 0) {
+    if (layout == 2 && tn_plain(e) && tn_long_k(M, N, K, e.k_keep != nullptr, sw) && (K % PP_BK) != 0) {
         const int K0 = K / BKT * BKT, kps = ((K + splits - 1) / splits + BKT - 1) / BKT * BKT;
         p.n_parts = 2;
         p.err = gemm_plan_part(p.part[0], layout, M, N, 0, K0, lda, ldb, ldc, e, e.assign != 0, (K + kps - 1) / kps, sw);
@@ -1903,6 +1917,42 @@ static GemmPlan gemm_plan(int layout, int M, int N, int K, long lda, long ldb, l
     p.n_parts = 1;
     p.err = gemm_plan_part(p.part[0], layout, M, N, 0, K, lda, ldb, ldc, e, e.assign != 0, splits, sw);
     return p;
+}
+
+// ---- split-K policy ---------------------------------------------------------------------------------------------------------------------
+// The factor a caller should pass as `splits` (the caller owns the workspace, so it has to know the factor before the call).  Pure, like the plan,
+// and written with the plan's predicates and tile constants: a threshold that moves there moves the factor with it.
+constexpr int TN_SPLIT_MIN_K = 256;                          // a weight-gradient split is worth at least this many contraction rows
+static int clamp_splits(int want, int most) { return want < most ? (want > 1 ? want : 1) : (most > 1 ? most : 1); }
+
+// One weight-gradient call, matched to the tile the plan gives it.  Measured on MI355X (tools/tn_probe.py): every tile holds one block per CU and is
+// fastest IN ISOLATION when tiles x splits lands just under 256; in the step these launches share the chip with the input-gradient chain of the
+// compute stream, which is the critical path, and about half the CUs (tn_blocks) is the better target (fewer partial tiles through the workspace,
+// CUs left to the other stream).  keep: the call has drop-path k_keep rows; their row groups are taken to fit the large tiles (the shipped ones
+// do: whole samples), since whoever asks does not know the group size yet.
+static int tn_splits(int M, int N, int K, bool keep, const GemmSwitches& sw) {
+    int kind = tn_tile_kind(M, N, K, nullptr, 1, sw);
+    // a ragged long contraction: the factor is for the first part, K rounded down to the k-tile (gemm_plan).  This also holds for K % 64 == 32 on an
+    // output the ping-pong kernel does not take (N % 256 != 0), which the plan does NOT split off and runs on 128 x 128 tiles: the factor such a
+    // shape had before the policy moved here, kept as it was (no shipped shape is one)
+    if (!kind && tn_long_k(M, N, K, keep, sw)) kind = tn_tile_kind(M, N, K / BKT * BKT, nullptr, 1, sw);
+    if (kind) {
+        const int tiles = ((M + BIG_BM - 1) / BIG_BM) * (kind == 2 ? N / 256 : (N + BN - 1) / BN);
+        return clamp_splits(tiles <= sw.tn_blocks ? sw.tn_blocks / tiles : 1, K / TN_SPLIT_MIN_K);
+    }
+    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);                 // 128 x 128 tiles: two blocks per CU
+    if (tiles >= 200) return 1;
+    return clamp_splits(tiles > 128 ? 5 : 256 / tiles, (K + TN_SPLIT_MIN_K - 1) / TN_SPLIT_MIN_K);
+}
+// A forward / input-gradient call whose output is too small to fill the chip while K is long (d_hidden = dlogits . W_dec: K = vocabulary)
+static int nn_splits(int M, int N, int K) {
+    if (K < 4096 || (N % 8) != 0) return 1;
+    if (nn_sk_huge(M, N, K)) {                               // 256 x 256 tiles: one block per CU
+        const int tiles = ((M + BIG_BM - 1) / BIG_BM) * (N / 256);
+        return tiles < 128 ? clamp_splits(256 / tiles, K / 1024) : 1;
+    }
+    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+    return tiles < 256 ? clamp_splits(512 / tiles, K / 1024) : 1;
 }
 
 // ---- entries ----------------------------------------------------------------------------------------------------------------------------
@@ -1977,14 +2027,28 @@ static void plan_report(const GemmLaunch& l, lav_gemm_launch_info* out, int max_
     if (n < max_out) out[n] = {gemm_kernels[l.kern].name, l.tile_m, l.tile_n, l.grid, (unsigned)gemm_kernels[l.kern].threads};
     ++n;
 }
+// ws (optional) is raised to the LAV_WS_SPLITK bytes the call requests: its parts run one after the other on one stream and share the workspace
 static int gemm_plan_query(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits,
-                           lav_gemm_launch_info* out, int max_out, int& n) {
+                           lav_gemm_launch_info* out, int max_out, int& n, size_t* ws = nullptr) {
     lav_gemm_epilogue e;
     if (int rc = gemm_check_args(layout, M, N, K, false, nullptr, lda, nullptr, ldb, nullptr, ldc, epi, e, splits)) return rc;
     const GemmPlan p = gemm_plan(layout, M, N, K, lda, ldb, ldc, e, splits, gemm_sw);
     if (int rc = gemm_plan_error(p, layout, N, K, ldc)) return rc;
-    for (int i = 0; i < p.n_parts; ++i) { plan_report(p.part[i].gemm, out, max_out, n); plan_report(p.part[i].reduce, out, max_out, n); }
+    for (int i = 0; i < p.n_parts; ++i) {
+        plan_report(p.part[i].gemm, out, max_out, n); plan_report(p.part[i].reduce, out, max_out, n);
+        if (ws && p.part[i].ws_bytes > *ws) *ws = p.part[i].ws_bytes;
+    }
     return LAV_OK;
+}
+// the split factor of one call (splits <= 0: the library's own) and the workspace it takes; no device needed
+extern "C" int lav_gemm_splits(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits, size_t* ws_bytes) {
+    LAV_REQUIRE(M > 0 && N > 0 && K > 0, "lav_gemm_splits: empty problem M=%d N=%d K=%d", M, N, K);
+    if (splits <= 0) splits = layout == 2 ? tn_splits(M, N, K, epi && epi->k_keep, gemm_sw) : nn_splits(M, N, K);
+    int n = 0;
+    if (ws_bytes) *ws_bytes = 0;
+    if (ws_bytes)
+        if (int rc = gemm_plan_query(layout, M, N, K, lda, ldb, ldc, epi, splits, nullptr, 0, n, ws_bytes)) return rc;
+    return splits;
 }
 // probe hook: the launches lav_gemm_bf16 would make for this call, without making them (no device needed)
 extern "C" int lav_gemm_plan(int layout, int M, int N, int K, long lda, long ldb, long ldc, const lav_gemm_epilogue* epi, int splits,
@@ -2025,7 +2089,7 @@ static TnGroupPlan tn_group_plan(int n_jobs, const lav_gemm_tn_job* jobs, int sp
     for (int j = 0; j < n_jobs; ++j) {
         const lav_gemm_tn_job& q = jobs[j];
         int sp = splits;
-        if (sp > q.K / 256) sp = q.K / 256 > 0 ? q.K / 256 : 1;
+        if (sp > q.K / TN_SPLIT_MIN_K) sp = q.K / TN_SPLIT_MIN_K > 0 ? q.K / TN_SPLIT_MIN_K : 1;
         p.k_per_split[j] = ((q.K + sp - 1) / sp + BKT - 1) / BKT * BKT;
         p.splits[j] = (q.K + p.k_per_split[j] - 1) / p.k_per_split[j];
         p.ws_tiles[j] = ((q.M + BIG_BM - 1) / BIG_BM) * ((q.N + BN - 1) / BN);
@@ -2106,4 +2170,32 @@ extern "C" int lav_gemm_tn_grouped_plan(int n_jobs, const lav_gemm_tn_job* jobs,
     plan_report({GK_PP_GROUP, (unsigned)p.blocks, 256, 256}, out, max_out, n);
     if (p.rblocks) plan_report({GK_TN_REDUCE_GROUP, (unsigned)p.rblocks, 256, BN}, out, max_out, n);
     return n;
+}
+
+// the group factor over jobs that fit the grouped launch (tn_group_fits): tn_group_blocks workgroups, at least TN_SPLIT_MIN_K contraction rows each
+static int tn_group_splits(int n_jobs, const lav_gemm_tn_job* jobs, const GemmSwitches& sw) {
+    int tiles = 0, K = jobs[0].K;
+    for (int j = 0; j < n_jobs; ++j) {
+        tiles += ((jobs[j].M + BIG_BM - 1) / BIG_BM) * (jobs[j].N / 256);
+        if (jobs[j].K < K) K = jobs[j].K;
+    }
+    const int blocks = tiles >= 96 ? sw.tn_group_blocks_wide : sw.tn_group_blocks;
+    return clamp_splits((int)nearbyint((double)blocks / tiles), K / TN_SPLIT_MIN_K);          // (halves round to even, as they always did)
+}
+// the split factors of a stage's weight gradients and the workspace they take; no device needed
+extern "C" int lav_gemm_tn_splits(int n_jobs, lav_gemm_tn_job* jobs, int splits, size_t* ws_bytes) {
+    LAV_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= 4, "lav_gemm_tn_splits: 1 ... 4 jobs (got %d)", n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        lav_gemm_tn_job& q = jobs[j];
+        LAV_REQUIRE(q.M > 0 && q.N > 0 && q.K > 0, "lav_gemm_tn_splits: empty problem M=%d N=%d K=%d", q.M, q.N, q.K);
+        if (q.fallback_splits <= 0) q.fallback_splits = tn_splits(q.M, q.N, q.K, q.k_keep != nullptr, gemm_sw);
+    }
+    const int group = !tn_group_fits(n_jobs, jobs, false, gemm_sw) ? 0 : splits > 0 ? splits : tn_group_splits(n_jobs, jobs, gemm_sw);
+    if (ws_bytes) *ws_bytes = group ? tn_group_plan(n_jobs, jobs, group).ws_bytes : 0;
+    for (int j = 0, n = 0; ws_bytes && j < n_jobs; ++j) {
+        const lav_gemm_tn_job& q = jobs[j];
+        const lav_gemm_epilogue e = tn_job_epilogue(q);
+        if (int rc = gemm_plan_query(2, q.M, q.N, q.K, q.lda, q.ldb, q.ldc, &e, q.fallback_splits, nullptr, 0, n, ws_bytes)) return rc;
+    }
+    return group;
 }

@@ -152,7 +152,7 @@ def dw_gemm(A, Bm, M, N, Kd, **kw):
 class DwGroup:
     """The weight-gradient GEMMs of one stage collected and issued as ONE grouped launch on the weight-gradient stream (lav_gemm_tn_grouped;
     the stage-level C entries do the same from C).  add() has dw_gemm's meaning; launch() after the last operand was produced.  Without the
-    side stream or with LAV_GEMM_TN_GROUP=0 every add() launches at once, as dw_gemm does."""
+    side stream or with grouping switched off every add() launches at once, as dw_gemm does."""
 
     def __init__(self, shapes, Kd):
         self.gs = K.group_splits_for(shapes, Kd) if _DW_SIDE else 0
@@ -170,13 +170,14 @@ class DwGroup:
             self.jobs = []
 
 
-def _stage_bwd(entry, fields, shapes, splits, gs, device, operands):
-    """a stage-level backward entry (K.swin_block_bwd / K.bert_layer_bwd): it issues the stage's weight-gradient GEMMs on the weight-gradient
-    stream itself (None: in line), so their `operands` are recorded there -- not to be recycled before that stream ran"""
+def _stage_bwd(entry, fields, shapes, Kd, rpg, device, operands):
+    """a stage-level backward entry (K.swin_block_bwd / K.bert_layer_bwd): it issues the stage's weight-gradient GEMMs (outputs `shapes` over Kd
+    token rows, rpg: K.ensure_stage_workspaces) on the weight-gradient stream itself (None: in line), so their `operands` are recorded there --
+    not to be recycled before that stream ran"""
     side = dw_stream(device) if _DW_SIDE else None
     raw = side.cuda_stream if side is not None else None
     _arm_join()
-    K.ensure_stage_workspaces(shapes, splits, gs, raw)
+    K.ensure_stage_workspaces(shapes, Kd, rpg, raw)
     entry(fields, raw)
     for t in operands if side is not None else ():
         t.record_stream(side)
@@ -451,7 +452,7 @@ class SwinBlockFn(torch.autograd.Function):
         fwd = _swin_fwd_values(ctx.c_head, dp_attn, dp_mlp, x, y1, st, qkv, ao, lse, x_mid, y2, h_pre, h, ctx.c_out)
         fields = _SB_BWD_PLACE(fwd + (dy.data_ptr(), alpha, alpha) + ctx.c_consts["bwd"] + splits + tuple(
             t.data_ptr() for t in (dh, d_y2, d_mid, d_ao, dqkv, d_y1, dx)) + (gs, _assign_mask(am)))       # labelled _SB_BWD_NAMES
-        _stage_bwd(K.swin_block_bwd, fields, ((3 * Cn, Cn), (Cn, Cn), (4 * Cn, Cn), (Cn, 4 * Cn)), splits, gs, dev,
+        _stage_bwd(K.swin_block_bwd, fields, ((3 * Cn, Cn), (Cn, Cn), (4 * Cn, Cn), (Cn, 4 * Cn)), M, (0, ctx.rpg, 0, ctx.rpg) if has_dp else None, dev,
                    (dy, h, dh, y2, d_mid, ao, dqkv, y1, qkv, d_ao, lse) + ((dp_attn, dp_mlp) if has_dp else ()))
         if ctx.notify and ctx.arena is not None:
             ctx.arena.notify(ctx.notify)
@@ -1006,7 +1007,7 @@ class BertLayerFn(torch.autograd.Function):
         fwd = _bert_fwd_values(ctx.c_head, key_mask, resln_t, x, qkv, cx, lse, pre1, st1, x1, h_pre, h, pre2, st2, ctx.c_y)
         fields = _BL_BWD_PLACE(fwd + (dy.data_ptr(),) + c["bwd"] + splits + tuple(
             t.data_ptr() for t in (d_pre2, d_dense2, dh, d_x1, d_pre1, d_dense1, d_cx, dqkv, dx)) + (gs, _assign_mask(am)))     # labelled _BL_BWD_NAMES
-        _stage_bwd(K.bert_layer_bwd, fields, ((3 * Hd, Hd), (Hd, Hd), (F, Hd), (Hd, F)), splits, gs, dev, (d_dense2, h, dh, x1, d_dense1, cx, dqkv, x))
+        _stage_bwd(K.bert_layer_bwd, fields, ((3 * Hd, Hd), (Hd, Hd), (F, Hd), (Hd, F)), R, None, dev, (d_dense2, h, dh, x1, d_dense1, cx, dqkv, x))
         return None, dx, None, None, None, None, None, None, None, None, None, None
 
     @staticmethod

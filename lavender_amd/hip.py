@@ -72,17 +72,21 @@ def release_retired_workspaces():
     _retired.clear()
 
 
-def tn_need(M, N, splits):
-    """upper bound of the split-K workspace bytes of one weight-gradient / split-K GEMM (256 x 256 fp32 partial tiles per split)"""
-    return 0 if splits <= 1 else int(splits) * ((M + 255) // 256) * ((N + 255) // 256) * 262144
+def _split_query(entry, *call):
+    """lav_gemm_splits / lav_gemm_tn_splits: (the split factor the entry answers with, the split-K workspace bytes the call will request)"""
+    need = C.c_size_t()
+    rc = entry(*call, need)
+    if rc < 0:
+        L.check(rc, entry.__name__)
+    return rc, need.value
 
 
-def ensure_stage_workspaces(shapes, splits, group_splits, side_stream_ptr):
-    """before a stage-level backward entry: LayerNorm scratch on the current stream, split-K partial tiles on the stream that runs the weight gradients"""
+def ensure_stage_workspaces(shapes, Kd, rpg, side_stream_ptr):
+    """before a stage-level backward entry: LayerNorm scratch on the current stream, split-K partial tiles on the stream that runs the weight
+    gradients `shapes` (M, N) over Kd token rows (rpg[j] > 0: output j skips drop-path rows in groups of that many)"""
     ensure_workspace(WS_LN_PARTIALS)
     ensure_workspace(WS_LN_DEFER)
-    need = sum(tn_need(M, N, max(s, group_splits)) for (M, N), s in zip(shapes, splits))
-    ensure_workspace(WS_SPLITK, need, side_stream_ptr)
+    ensure_workspace(WS_SPLITK, _tn_splits(shapes, Kd, rpg)[2], side_stream_ptr)
 
 
 def next_seed():
@@ -162,7 +166,7 @@ def gemm(layout, A, B, M, N, K, out=None, out_dtype=bf16, bias=None, act=0, prea
                         _dp(k_keep), int(k_rows_per_group), _dp(rowsum_a), int(preact_is_grad), int(gelu_in_is_grad), int(res32),
                         _dp(a_rowmap), _dp(res_rowmap), ln_m, ln_r, ln_g, ln_b, hm_h, hm_d, hm_rows, int(bool(c_pad_writable)), int(bool(assign)))
     if splits > 1:
-        ensure_workspace(WS_SPLITK, tn_need(M, N, splits))
+        ensure_workspace(WS_SPLITK, _split_query(L.lib.lav_gemm_splits, layout, M, N, K, _ld(A), _ld(B), ldc, ref, splits)[1])
     rc = L.lib.lav_gemm_bf16(_s(), layout, M, N, K, A.data_ptr(), _ld(A), B.data_ptr(), _ld(B), out.data_ptr(), ldc, ref, splits)
     if rc != 0:
         L.check(rc, "lav_gemm_bf16")
@@ -180,7 +184,7 @@ def gemm_tn_grouped(jobs, splits):
         q.rowsum_a, q.k_keep = _dp(j.get("rowsum_a")), _dp(j.get("k_keep"))
         q.k_rows_per_group, q.alpha, q.fallback_splits = int(j.get("k_rows_per_group", 1)), float(j.get("alpha", 1.0)), int(j.get("fallback_splits", 1))
         q.assign = int(bool(j.get("assign", False)))
-    ensure_workspace(WS_SPLITK, sum(tn_need(q.M, q.N, max(int(splits), q.fallback_splits)) for q in arr))
+    ensure_workspace(WS_SPLITK, _split_query(L.lib.lav_gemm_tn_splits, len(jobs), arr, max(int(splits), 1))[1])
     rc = L.lib.lav_gemm_tn_grouped(_s(), len(jobs), arr, int(splits))
     if rc != 0:
         L.check(rc, "lav_gemm_tn_grouped")
@@ -264,58 +268,47 @@ def bert_layer_bwd(fields, side_stream):
     _stage_call("lav_bert_layer_bwd", BL_BWD, fields, side_stream)
 
 
-import os as _os
-_TN_BLOCKS = int(_os.environ.get("LAV_TN_BLOCKS", "128"))      # target blocks per weight-gradient GEMM (probe hook; 128 vs 192 etc.: profiles/r04_gemm_experiments.md section 8)
-_TN_MINM = int(_os.environ.get("LAV_GEMM_TN_MINM", "160"))     # fewest output rows that still take the 256-row weight-gradient tiles (gemm.hip: tn_min_m)
+# ---- split-K policy: the library's (gemm.hip, beside the route plan); these ask for it ---------------------------------------------------------
+_tn_cache = {}       # per shape: a ctypes job array per stage call would cost more than the arithmetic did when it lived here
+
+
+def gemm_select(which, value):
+    """lav_gemm_select.  The switches move the split factors, so everything cached from the policy is dropped: call this, never the library's
+    entry directly."""
+    _tn_cache.clear()
+    return L.lib.lav_gemm_select(which, value)
+
+
+def _tn_splits(shapes, K, rpg=None):
+    """lav_gemm_tn_splits for the weight gradients `shapes` (M, N) with contraction K (rpg[j] > 0: drop-path keep rows in groups of that many):
+    (split factor of each output alone, group factor or 0, split-K workspace bytes that cover either way of launching them)"""
+    key = (shapes, K, rpg)
+    r = _tn_cache.get(key)
+    if r is None:
+        arr = (L.GemmTnJob * len(shapes))()
+        for q, (M, N), g in zip(arr, shapes, rpg or (0,) * len(shapes)):
+            q.M, q.N, q.K, q.lda, q.ldb, q.ldc = M, N, K, (M + 7) // 8 * 8, (N + 7) // 8 * 8, (N + 3) // 4 * 4
+            q.k_keep, q.k_rows_per_group = (8 if g else None), g          # (only tested for presence)
+        gs, need = _split_query(L.lib.lav_gemm_tn_splits, len(arr), arr, 0)
+        r = _tn_cache[key] = (tuple(q.fallback_splits for q in arr), gs, need)
+    return r
 
 
 def splits_for(M, N, K, keep=False):
-    """split-K factor for weight-gradient GEMMs, matched to the kernel lav_gemm_bf16 picks for the shape (256x256 tiles
-    when M >= 256, N % 256 == 0 and K % 64 == 0; 256x128 when only N % 256 fails; else 128x128).  Measured on MI355X
-    (tools/tn_probe.py): every variant holds one block per CU and is fastest IN ISOLATION when tiles x splits lands just under
-    256; in the step these launches share the chip with the input-gradient chain of the compute stream, which is the critical
-    path, and about half the CUs is the better target (fewer partial tiles through the workspace, CUs left to the other stream)."""
-    if M >= (_TN_MINM if N >= 512 else max(_TN_MINM, 256)) and (K % 64 == 0 or (K % 32 == 0 and N % 256 == 0) or (K >= 2048 and not keep)):   # ragged long K: lav_gemm_bf16 splits off the < 64-row tail
-        tiles = ((M + 255) // 256) * (N // 256 if N % 256 == 0 else (N + 127) // 128)
-        return int(max(1, min(_TN_BLOCKS // tiles if tiles <= _TN_BLOCKS else 1, K // 256)))
-    tiles = ((M + 127) // 128) * ((N + 127) // 128)
-    if tiles >= 200:
-        return 1
-    s = 5 if tiles > 128 else max(1, 256 // tiles)
-    return int(max(1, min(s, 256, (K + 255) // 256)))
-
-
-_TN_GROUP = _os.environ.get("LAV_GEMM_TN_GROUP", "1") != "0"
-_TN_GROUP_BLOCKS = int(_os.environ.get("LAV_TN_GROUP_BLOCKS", "192"))      # target workgroups of a grouped weight-gradient launch (sweep: profiles/r04_late_experiments.md section 11)
-_TN_GROUP_BLOCKS_WIDE = int(_os.environ.get("LAV_TN_GROUP_BLOCKS_WIDE", str(_TN_GROUP_BLOCKS)))   # probe hook: the same for groups of >= 96 tiles (the fusion layers)
+    """split-K factor for a weight-gradient GEMM, matched to the tile lav_gemm_bf16 runs the shape on (gemm.hip: tn_splits)"""
+    return _tn_splits(((M, N),), K, (K,) if keep else None)[0][0]          # (the factor depends on keep rows being there, not on their grouping)
 
 
 def group_splits_for(shapes, K):
     """split factor of a GROUPED weight-gradient launch over the (M, N) outputs `shapes` with contraction K (lav_gemm_tn_grouped), 0 when the
     group does not apply (an output the 256 x 256 kernel cannot take: the stage entries then launch one by one with splits_for)."""
-    if not _TN_GROUP or K % 32:
-        return 0
-    tiles = 0
-    for M, N in shapes:
-        if N % 256 or M < (_TN_MINM if N >= 512 else max(_TN_MINM, 256)):
-            return 0
-        tiles += ((M + 255) // 256) * (N // 256)
-    return int(max(1, min(round((_TN_GROUP_BLOCKS_WIDE if tiles >= 96 else _TN_GROUP_BLOCKS) / tiles), K // 256)))
+    return _tn_splits(tuple(shapes), K)[1]
 
 
 def splits_nn(M, N, K):
     """split-K factor for a forward / input-gradient GEMM whose output is too small to fill the chip while K is long
-    (d_hidden = dlogits . W_dec: K = vocabulary).  256x256 tiles (one block per CU) when M >= 256, N % 256 == 0 and
-    K % 64 == 0, else 128x128 tiles (two blocks per CU)."""
-    if K < 4096 or N % 8:
-        return 1
-    if M >= 256 and N % 256 == 0 and K % 64 == 0:
-        tiles = ((M + 255) // 256) * (N // 256)
-        return int(max(1, min(256 // tiles, K // 1024))) if tiles < 128 else 1
-    tiles = ((M + 127) // 128) * ((N + 127) // 128)
-    if tiles >= 256:
-        return 1
-    return int(max(1, min(512 // tiles, K // 1024)))
+    (d_hidden = dlogits . W_dec: K = vocabulary): gemm.hip nn_splits"""
+    return L.lib.lav_gemm_splits(1, M, N, K, 0, 0, 0, None, 0, None)
 
 
 def _gather(g):

@@ -365,3 +365,46 @@ def grouped_route(jobs, splits, tn_min_m=160, pp_tn=True):
     if any(s > 1 for s in sp):
         r.append(("tn_reduce_group_kernel", (256, 128)))
     return r
+
+
+# ---- the split-K policy as lavender_amd/hip.py held it before it moved into the library (gemm.hip: tn_splits, nn_splits, tn_group_splits): the
+# bodies verbatim, the module constants they read as parameters.  tests/test_gemm_layernorm_bounds_host.py holds the library's answers to these.
+def splits_for(M, N, K, keep=False, tn_min_m=160, tn_blocks=128):
+    _TN_MINM, _TN_BLOCKS = tn_min_m, tn_blocks
+    if M >= (_TN_MINM if N >= 512 else max(_TN_MINM, 256)) and (K % 64 == 0 or (K % 32 == 0 and N % 256 == 0) or (K >= 2048 and not keep)):   # ragged long K: lav_gemm_bf16 splits off the < 64-row tail
+        tiles = ((M + 255) // 256) * (N // 256 if N % 256 == 0 else (N + 127) // 128)
+        return int(max(1, min(_TN_BLOCKS // tiles if tiles <= _TN_BLOCKS else 1, K // 256)))
+    tiles = ((M + 127) // 128) * ((N + 127) // 128)
+    if tiles >= 200:
+        return 1
+    s = 5 if tiles > 128 else max(1, 256 // tiles)
+    return int(max(1, min(s, 256, (K + 255) // 256)))
+
+
+def group_splits_for(shapes, K, tn_min_m=160, tn_group=True, tn_group_blocks=192, tn_group_blocks_wide=192):
+    _TN_MINM, _TN_GROUP, _TN_GROUP_BLOCKS, _TN_GROUP_BLOCKS_WIDE = tn_min_m, tn_group, tn_group_blocks, tn_group_blocks_wide
+    if not _TN_GROUP or K % 32:
+        return 0
+    tiles = 0
+    for M, N in shapes:
+        if N % 256 or M < (_TN_MINM if N >= 512 else max(_TN_MINM, 256)):
+            return 0
+        tiles += ((M + 255) // 256) * (N // 256)
+    return int(max(1, min(round((_TN_GROUP_BLOCKS_WIDE if tiles >= 96 else _TN_GROUP_BLOCKS) / tiles), K // 256)))
+
+
+def splits_nn(M, N, K):
+    if K < 4096 or N % 8:
+        return 1
+    if M >= 256 and N % 256 == 0 and K % 64 == 0:
+        tiles = ((M + 255) // 256) * (N // 256)
+        return int(max(1, min(256 // tiles, K // 1024))) if tiles < 128 else 1
+    tiles = ((M + 127) // 128) * ((N + 127) // 128)
+    if tiles >= 256:
+        return 1
+    return int(max(1, min(512 // tiles, K // 1024)))
+
+
+def tn_need(M, N, splits):
+    """upper bound of the split-K workspace bytes of one weight-gradient / split-K GEMM (256 x 256 fp32 partial tiles per split)"""
+    return 0 if splits <= 1 else int(splits) * ((M + 255) // 256) * ((N + 255) // 256) * 262144

@@ -161,7 +161,7 @@ def test_route_table_host_selector():
 
 
 # ---- the library's own route plan (lav_gemm_plan, no device) against the host copy ------------------------------------------------------------
-SEL = {"ps": 11, "h192": 7, "h192l": 9, "pp_tn": 2, "tn_min_m": 12, "group_n": 6, "dbg": 5}
+SEL = {"ps": 11, "h192": 7, "h192l": 9, "pp_tn": 2, "tn_min_m": 12, "group_n": 6, "dbg": 5, "tn_group": 13}
 _PTR = 4096          # a non-null, 16-byte aligned stand-in: the plan only tests the epilogue's pointers for presence
 
 
@@ -203,7 +203,7 @@ def _plan(layout, M, N, K, lda, ldb, ldc, epi, splits):
     return _launches(n, out, (layout, M, N, K, lda, ldb, ldc, epi, splits))
 
 
-def _grouped_plan(jobs, splits):
+def _job_array(jobs):
     from lavender_amd import _lib
     arr = (_lib.GemmTnJob * len(jobs))()
     for q, j in zip(arr, jobs):
@@ -211,24 +211,30 @@ def _grouped_plan(jobs, splits):
         if j.get("k_keep_rpg"):
             q.k_keep, q.k_rows_per_group = _PTR, j["k_keep_rpg"]
         q.alpha, q.fallback_splits = 1.0, j.get("fallback_splits", 1)
+    return arr
+
+
+def _grouped_plan(jobs, splits):
+    from lavender_amd import _lib
+    arr = _job_array(jobs)
     out = (_lib.GemmLaunchInfo * 16)()
     return _launches(_lib.lib.lav_gemm_tn_grouped_plan(len(jobs), arr, splits, out, 16), out, (jobs, splits))
 
 
 class _switches:
-    """lav_gemm_select overrides for a block, restored afterwards"""
+    """lav_gemm_select overrides for a block (through hip.gemm_select: the split factors hip.py caches follow the switches), restored afterwards"""
 
     def __init__(self, **over):
         self.over = over
 
     def __enter__(self):
-        from lavender_amd import _lib
-        self.old = {k: _lib.lib.lav_gemm_select(SEL[k], int(v)) for k, v in self.over.items()}
+        from lavender_amd import hip
+        self.old = {k: hip.gemm_select(SEL[k], int(v)) for k, v in self.over.items()}
 
     def __exit__(self, *exc):
-        from lavender_amd import _lib
+        from lavender_amd import hip
         for k, v in self.old.items():
-            _lib.lib.lav_gemm_select(SEL[k], v)
+            hip.gemm_select(SEL[k], v)
 
 
 def _route_kw(over):
@@ -414,12 +420,9 @@ def test_plan_matches_route_on_a_random_sweep():
 def test_grouped_plan_matches_route_and_hip_split_heuristic():
     """random groups of 1 ... 4 weight-gradient jobs with a common contraction: lav_gemm_tn_grouped_plan against gemm_bounds.grouped_route at each
     pp_tn / tn_min_m setting, and hip.group_splits_for(shapes, K) > 0 exactly when the library takes the grouped launch (jobs without k_keep,
-    which hip.py does not see; hip.py reads LAV_GEMM_TN_MINM itself: its value must be the library's)"""
+    which group_splits_for is not told of)"""
     import numpy as np
-    from lavender_amd import _lib, hip
-    mm = _lib.lib.lav_gemm_select(SEL["tn_min_m"], 160)
-    _lib.lib.lav_gemm_select(SEL["tn_min_m"], mm)
-    assert mm == hip._TN_MINM, (mm, hip._TN_MINM)
+    from lavender_amd import hip
     rng = np.random.default_rng(7)
     grouped = 0
     for over in (dict(), dict(pp_tn=0), dict(tn_min_m=256), dict(tn_min_m=300, pp_tn=1)):
@@ -440,6 +443,113 @@ def test_grouped_plan_matches_route_and_hip_split_heuristic():
             if not over and not rpg:
                 assert (hip.group_splits_for([(j["M"], j["N"]) for j in jobs], K) > 0) == is_group, (jobs, got)
     assert grouped > 200
+
+
+# ---- the split-K policy (lav_gemm_splits / lav_gemm_tn_splits, no device) against the copy of what hip.py computed before (gemm_bounds) ---------
+def _plan_ws(layout, M, N, K, lda, ldb, ldc, epi, splits):
+    """split-K workspace bytes of a call, read off the launches of the library's route plan: a reduction pass sums one fp32 partial tile per
+    workgroup of the GEMM launch in front of it"""
+    import ctypes as C
+    from lavender_amd import _lib
+    out = (_lib.GemmLaunchInfo * 4)()
+    n = _lib.lib.lav_gemm_plan(layout, M, N, K, lda, ldb, ldc, C.byref(_c_epilogue(epi)), splits, out, 4)
+    assert n > 0, (layout, M, N, K, epi, splits, _lib.lib.lav_last_error())
+    return max([out[i - 1].grid * out[i - 1].tile_rows * out[i - 1].tile_cols * 4 for i in range(1, n) if b"reduce" in out[i].kernel], default=0)
+
+
+def _group_ws(jobs, gs):
+    """the same of a grouped launch (gemm.hip tn_group_plan): 256-row partial tiles of every job that is split"""
+    ws = 0
+    for q in jobs:
+        s = max(1, min(gs, q["K"] // 256))
+        kps = ((q["K"] + s - 1) // s + 63) // 64 * 64
+        sp = -(-q["K"] // kps)
+        ws += sp * -(-q["M"] // 256) * (q["N"] // 128) * 256 * 128 * 4 if sp > 1 else 0
+    return ws
+
+
+def _check_split_policy(shapes, K, rpg, **par):
+    """one group of weight gradients `shapes` over K rows (rpg: drop-path rows per group, 0 = none) and each of them alone: factors against the
+    copy evaluated at `par`, workspace bytes against the plan and the old bound.  Returns (group factor, tiles of the group)."""
+    import ctypes as C
+    from lavender_amd import _lib, hip
+    mm = {k: par[k] for k in ("tn_min_m",) if k in par}
+    want = [GB.splits_for(M, N, K, bool(rpg), **mm) for M, N in shapes]
+    epi = dict(out="acc", rowsum=True, **({"k_keep_rpg": rpg} if rpg else {}))
+    for (M, N), w in zip(shapes, want):
+        assert hip.splits_for(M, N, K, bool(rpg)) == w, (M, N, K, rpg, par, hip.splits_for(M, N, K, bool(rpg)), w)
+        (lda, ldb), ldc, ws = _ld(2, M, N, K), (N + 3) // 4 * 4, C.c_size_t(1 << 60)
+        got = _lib.lib.lav_gemm_splits(2, M, N, K, lda, ldb, ldc, C.byref(_c_epilogue(epi)), 0, C.byref(ws))
+        assert got == w, (M, N, K, rpg, par, got, w, _lib.lib.lav_last_error())
+        assert ws.value == _plan_ws(2, M, N, K, lda, ldb, ldc, epi, w) <= GB.tn_need(M, N, w), (M, N, K, rpg, par, ws.value, GB.tn_need(M, N, w))
+        assert hip.splits_nn(K, N, M) == GB.splits_nn(K, N, M), (K, N, M)           # the same numbers as a long-K forward call, contraction M
+    want_gs = GB.group_splits_for(shapes, K, **par)
+    assert hip.group_splits_for(shapes, K) == want_gs, (shapes, K, par, hip.group_splits_for(shapes, K), want_gs)
+    jobs = [dict(M=M, N=N, K=K, k_keep_rpg=rpg, fallback_splits=0) for M, N in shapes]
+    arr, ws = _job_array(jobs), C.c_size_t(1 << 60)
+    gs = _lib.lib.lav_gemm_tn_splits(len(jobs), arr, 0, C.byref(ws))
+    assert gs >= 0 and [q.fallback_splits for q in arr] == want, (jobs, par, gs, [q.fallback_splits for q in arr], want)
+    for j, w in zip(jobs, want):
+        j["fallback_splits"] = w
+    is_group = _grouped_plan(jobs, max(gs, 1))[0][0] == "gemm_pp_group_kernel"
+    assert (gs > 0) == is_group and (gs == want_gs or (rpg and gs == 0)), (jobs, par, gs, want_gs)      # keep rows the kernel cannot take: one by one
+    ws_plan = max([_group_ws(jobs, gs) if gs else 0] + [_plan_ws(2, M, N, K, *_ld(2, M, N, K), (N + 3) // 4 * 4, epi, w) for (M, N), w in zip(shapes, want)])
+    assert ws.value == ws_plan <= sum(GB.tn_need(M, N, max(w, gs)) for (M, N), w in zip(shapes, want)), (jobs, par, gs, ws.value, ws_plan)
+    return gs, sum(-(-M // 256) * (N // 256) for M, N in shapes)
+
+
+def test_split_policy_matches_the_copy_on_the_bench_models():
+    """every nn.Linear and every stage group of cfg2 / cfg4 / cfg5, with and without drop-path rows, at the default switches"""
+    n = grouped = 0
+    for size, S, X, B, pairs in (("base", 224, 32, 32, None), ("large", 384, 32, 8, None), ("base", 224, 26, 8, 64)):
+        lin, groups = _model_linears(size, S, X, B, pairs)
+        for R, o, i, rpg in lin:
+            for keep in ((0, rpg) if rpg else (0,)):
+                _check_split_policy([(o, i)], R, keep)
+                n += 1
+        for shapes, K, rpg in groups:
+            for keep in ((0, rpg) if rpg else (0,)):
+                grouped += _check_split_policy(shapes, K, keep)[0] > 0
+                n += 1
+    print(f"{n} linears and groups, {grouped} grouped")
+    assert n > 150 and grouped > 0                           # (the cfg2 fusion layers, 45120 token rows, are grouped launches)
+
+
+def _random_group(rng):
+    """1 ... 4 weight-gradient outputs with a common contraction around every threshold of the policy: (shapes, K, rows per drop-path group)"""
+    if rng.random() < 0.45:                                  # a group the 256 x 256 kernel takes, on both sides of 96 tiles
+        K = 32 * int(rng.integers(1, 1500)) if rng.random() < 0.7 else _pick(rng, [7840, 30280 - 8, 45120, 224, 256, 288, 2048, 2080])
+        shapes = [(_pick(rng, [160, 161, 192, 256, 257, 384, 768, 1024, 1536, 3072, 4096]), 256 * int(rng.integers(2, 17))) for _ in range(int(rng.integers(1, 5)))]
+    else:
+        K = max(1, _pick(rng, [32 * int(rng.integers(1, 1500)), 64 * int(rng.integers(1, 750)), 2048 + int(rng.integers(-70, 71)), int(rng.integers(1, 256)),
+                               30280, 33840, 7840, int(rng.integers(1, 50000))]))
+        shapes = [(_pick(rng, [127, 128, 129, 159, 160, 161, 255, 256, 257, 300, 301, 512, 1000, 3072, 30522, int(rng.integers(1, 9000))]),
+                   max(4, _pick(rng, [128, 256]) * int(rng.integers(1, 25)) + _pick(rng, [0, 0, 0, 4, -4, 8, -8])))
+                  for _ in range(int(rng.integers(1, 5)))]
+    rpg = _pick(rng, [0, 0, 64, 245, 256, 32, 63, -(-K // 128), -(-K // 129), K])
+    return shapes, K, rpg
+
+
+@pytest.mark.parametrize("par", [dict(), dict(tn_min_m=256), dict(tn_min_m=300), dict(tn_group=0)], ids=lambda p: "-".join(f"{k}{v}" for k, v in p.items()) or "default")
+def test_split_policy_matches_the_copy_on_a_random_sweep(par):
+    """seeded groups of 1 ... 4 outputs (20 000 shapes and more at the default switches): M 127 ... 129, 159 ... 161, 255 ... 257 and larger, N multiples
+    of 128 and 256 +- 4 and 8, K multiples of 32 and 64, ragged on both sides of 2048 and below 256, drop-path rows on and off, groups on both sides of
+    96 tiles.  The library's factors equal the copy evaluated at the selected tn_min_m / tn_group; its workspace bytes are the plan's and within the
+    old bound."""
+    import numpy as np
+    rng = np.random.default_rng(1606 + len(par) + par.get("tn_min_m", 0))
+    shapes_n = groups = 0
+    side = [0, 0]
+    with _switches(**par):
+        while shapes_n < (20000 if not par else 4000):
+            shapes, K, rpg = _random_group(rng)
+            gs, tiles = _check_split_policy(shapes, K, rpg, **par)
+            shapes_n += len(shapes)
+            groups += gs > 0
+            side[tiles >= 96] += gs > 0
+    print(f"{shapes_n} shapes, {groups} grouped launches ({side[0]} below 96 tiles, {side[1]} from 96 up)")
+    assert par.get("tn_group", 1) == 0 or min(side) > (100 if not par else 20)
+    assert par.get("tn_group", 1) != 0 or groups == 0
 
 
 # ---- LayerNorm --------------------------------------------------------------------------------------------------------------------------

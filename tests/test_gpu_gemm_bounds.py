@@ -141,14 +141,14 @@ def _ps_rows(names):
 
 
 def _select(over):
-    from lavender_amd import _lib
-    return {k: _lib.lib.lav_gemm_select(SEL[k], int(v)) for k, v in over.items()}
+    from lavender_amd import hip
+    return {k: hip.gemm_select(SEL[k], int(v)) for k, v in over.items()}
 
 
 def _restore(old):
-    from lavender_amd import _lib
+    from lavender_amd import hip
     for k, v in old.items():
-        _lib.lib.lav_gemm_select(SEL[k], v)
+        hip.gemm_select(SEL[k], v)
 
 
 def _operands(layout, M, N, K, epi, seed):

@@ -127,13 +127,13 @@ def test_gemm_phase_shifted_tiles_are_bit_identical_to_the_two_phase_kernels(sha
         torch.cuda.synchronize()
         return out, kw.get("preact"), kw.get("colsum")
 
-    old = _lib.lib.lav_gemm_select(11, 0)
+    old = K().gemm_select(11, 0)
     try:
         ref = run()
-        _lib.lib.lav_gemm_select(11, 3)
+        K().gemm_select(11, 3)
         got = run()
     finally:
-        _lib.lib.lav_gemm_select(11, old)
+        K().gemm_select(11, old)
     assert torch.equal(got[0], ref[0])
     if ref[1] is not None: assert torch.equal(got[1], ref[1])
     if ref[2] is not None: close(got[2], ref[2], atol=1e-2, rtol=1e-4, what="column sums (atomics: order differs)")

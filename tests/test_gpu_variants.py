@@ -543,9 +543,9 @@ def test_stage_level_c_entries_match_the_per_kernel_path(size):
         torch.cuda.synchronize()
         return logits, {n: ar.params[n].grad.clone() for n in wnames}, ar.grad.clone()
 
-    keep, keep_group = E.STAGE_C, K._TN_GROUP
+    keep, keep_group = E.STAGE_C, K.gemm_select(13, 0)
     try:
-        K._TN_GROUP = False                                      # one weight-gradient launch per nn.Linear, as the per-kernel path issues them
+        # (lav_gemm_select 13 = tn_group, off from here:) one weight-gradient launch per nn.Linear, as the per-kernel path issues them
         ref_logits, ref, ref_all = run(False)
         for rep in range(3):
             logits, got, got_all = run(True)
@@ -555,7 +555,7 @@ def test_stage_level_c_entries_match_the_per_kernel_path(size):
             assert ((got_all - ref_all).norm() / ref_all.norm()).item() < 1e-5
         # the shipped form: a stage's four weight gradients as ONE grouped launch (lav_gemm_tn_grouped) -- other split factors, so the fp32
         # sums differ in their last bits; everything else is unchanged
-        K._TN_GROUP = True
+        K.gemm_select(13, 1)
         logits, got, got_all = run(True)
         assert torch.equal(logits[0], ref_logits[0]) and torch.equal(logits[1], ref_logits[1])
         for n in wnames:
@@ -563,7 +563,8 @@ def test_stage_level_c_entries_match_the_per_kernel_path(size):
             assert d <= 2e-5 * ref[n].norm().item() + 1e-12, (n, d, ref[n].norm().item())
         assert ((got_all - ref_all).norm() / ref_all.norm()).item() < 1e-5
     finally:
-        E.STAGE_C, K._TN_GROUP = keep, keep_group
+        E.STAGE_C = keep
+        K.gemm_select(13, keep_group)
 
 
 def test_gradients_are_whole_when_backward_returns_and_saved_tensors_may_move():

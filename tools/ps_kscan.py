@@ -8,8 +8,8 @@ bf = torch.bfloat16
 dev = "cuda"
 NSET = 6
 for sel, dbg in ((3, 0), (3, 1), (3, 2), (0, 0), (0, 1), (0, 2)):
-    L.lib.lav_gemm_select(11, sel)
-    L.lib.lav_gemm_select(5, dbg)
+    K.gemm_select(11, sel)
+    K.gemm_select(5, dbg)
     for (M, N) in ((45120, 3072), (45120, 768)):
         for epi in ("b", "none"):
             rows = []
@@ -36,4 +36,4 @@ for sel, dbg in ((3, 0), (3, 1), (3, 2), (0, 0), (0, 1), (0, 2)):
             slope = (t1 - t0) / ((k1 - k0) / 64)
             print(f"ps={sel} dbg={dbg} {M}x{N} " + "  ".join(f"K={k}: {t:6.1f}" for k, t in rows) + f"   us per k-step {slope:5.2f}, intercept {t0 - slope:6.1f} us", flush=True)
             break
-L.lib.lav_gemm_select(5, 0)
+K.gemm_select(5, 0)

@@ -13,7 +13,7 @@ NSET = 6
 
 
 def sel(v):
-    L.lib.lav_gemm_select(11, v)
+    K.gemm_select(11, v)
 
 
 def make(M, N, Kd, epi):
