@@ -814,6 +814,24 @@ int lav_answer_readout(void* stream, int n, int V, const void* logits, long ld, 
                        const int32_t* cand_host, int n_cand, int splits, void* workspace, size_t workspace_bytes, int32_t* pred, int32_t* rank,
                        int32_t* choice);
 
+/* lav_match_readout: the in-batch matching read-out of the MLM retrieval callers (main_retrieval_mlm.py:107-118, main_retmc_mlm.py:129-140): G groups
+ * of O candidates, candidate k = g * O + o.  t = logits[row[k], true_col], f = logits[row[k], false_col] (logits (n_rows, ld); dtype 0 = bf16,
+ * 1 = fp32; row == NULL means row[k] = k), both widened to fp32, s = t / (t + f) in fp32 on the RAW logits as the reference has it.
+ *   score[k]   s, when score is given; every NaN is stored as the one pattern 0x7fc00000
+ *   choice[g]  arg-max of s over o in the order of lav_answer_readout's choice: a NaN above every number, -0 = +0, the LOWEST o first among equal
+ *              values and among NaNs
+ *   hit[g]     choice[g] == gt[g], when hit is given (then gt must be); 0 where gt[g] lies outside [0, O)
+ * A row[k] outside [0, n_rows) reads nothing and its candidate scores "NaN-last": score[k] is that NaN pattern, but in the order it stands BELOW
+ * every number and below a NaN quotient (lowest o first among such candidates).  This is the one place where the order has a fourth class: a
+ * candidate that was not read must never win against one that was.  hip.match_readout rejects such an entry of a host row array instead.
+ * The same entry serves the (n, 2) fp32 block of lav_mlm_pair_readout (ld = 2, columns 0 / 1, row = NULL) and the reference's formulation (the
+ * bf16 (pairs * X, ld) logits, row[k] = the [MASK] row of pair k, columns = the "true" / "false" token ids).
+ * Rejected before any launch: G < 1, O < 1, a column outside [0, ld), dtype not 0 / 1, row == NULL with n_rows < G * O, hit without gt.
+ * One wave per group, lanes stride over o, the max is taken over the (key, ~o) integer word: identical results for every O and lane mapping; groups
+ * are walked with a grid-stride loop (any G).  No atomics, no workspace, no allocation, no synchronisation. */
+int lav_match_readout(void* stream, int G, int O, const void* logits, long ld, int dtype, const int32_t* row, long n_rows, int true_col,
+                      int false_col, const int32_t* gt, float* score, int32_t* choice, int32_t* hit);
+
 /* ---------------------------------------------------------------------------------------------
  * Process-wide probe switches: environment variables read ONCE by the library on first use (not part of the contract; every setting
  * computes the same results up to fp32 summation order unless stated).  They exist so that tools/ and profiles/ can A/B a kernel

@@ -15,6 +15,7 @@ from .retrieval_mlm import LAVENDER_Retrieval_MLM, Agent_Retrieval_MLM, LAVENDER
 from .captioning import LAVENDER_Captioning, Agent_Captioning, CaptioningLoss  # noqa: F401
 from .qa_mlm import (LAVENDER_QAOE_MLM, LAVENDER_QAMC_MLM, LAVENDER_RetMC_MLM, Agent_QAOE_MLM, Agent_QAMC_MLM,  # noqa: F401
                      Agent_RetMC_MLM)
+from .multi_task import LAVENDER_Multi_Task, Agent_Multi_Task, MetaLoader  # noqa: F401
 from .agent import Agent_Base, WarmupLinearLR, CrossEntropyIgnore  # noqa: F401
 
 VIOLET_Base = LAVENDER_Base

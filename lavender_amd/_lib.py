@@ -230,6 +230,7 @@ _SIGS = {
     # video-QA read-out (csrc/qa.hip)
     "lav_answer_readout_workspace_bytes": (C.c_size_t, [i32, i32]),
     "lav_answer_readout": (i32, [vp, i32, i32, vp, i64, i32, vp, vp, vp, i32, i32, vp, C.c_size_t, vp, vp, vp]),
+    "lav_match_readout": (i32, [vp, i32, i32, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp]),
     # fp32-I/O validation mode (csrc/validate.hip)
     "lav_v_gemm_f32": (i32, [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i32, vp, i64]),
     "lav_v_attention_f32": (i32, [vp, P(AttnDesc), vp, vp, vp]),

@@ -35,7 +35,9 @@ _DEFAULTS = dict(
     # captioning (main_caption.py, model_for_captioning.py:10-37)
     label_smoothing=0.0, drop_worst_ratio=0.0, drop_worst_after=0, max_gen_length=20,
     # video QA (main_qaoe_mlm.py, main_qamc_mlm.py): head, last layer and read-out on the labelled [MASK] rows only (qa_mlm.py)
-    qa_rows=False, size_option=5)
+    qa_rows=False, size_option=5,
+    # multi-task MLM fine-tuning (main_multi_task_mlm.py): the rows paths of multi_task.py
+    mt_rows=False)
 
 
 def parse_with_config(argv=None, defaults=None):

@@ -355,11 +355,11 @@ class Agent_Captioning(Agent_Base):
         assert predict_file.endswith('.tsv')
         return op.splitext(predict_file)[0] + '.eval.json'
 
-    def evaluate(self, ep, val_dataloader):
-        """main_caption.py:182-217: the prediction file under <path_output>/caption_predictions (skipped when it exists), then
+    def evaluate(self, ep, val_dataloader, subdir=None):
+        """main_caption.py:182-217: the prediction file under <path_output>/caption_predictions[/<subdir>] (skipped when it exists), then
         caption_metric(predict_file, caption_file) on rank 0, its result on every rank; None without a metric."""
         self._set_mode(False)
-        output_dir = op.join(self.args.path_output, "caption_predictions")
+        output_dir = op.join(self.args.path_output, "caption_predictions", *([subdir] if subdir else []))
         if is_main_process():
             os.makedirs(output_dir, exist_ok=True)
         synchronize()

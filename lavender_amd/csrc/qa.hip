@@ -192,3 +192,66 @@ extern "C" int lav_answer_readout(void* stream, int n, int V, const void* logits
     }
     return lav_check_launch("lav_answer_readout");
 }
+
+// ---- in-batch matching read-out (retrieval / lsmdc-mc evaluation): main_retrieval_mlm.py:107-118, main_retmc_mlm.py:129-140 ----------------------
+// One wave per group of O candidates, lanes stride over o; the arg-max is the integer max of the (key, ~o) word above, so it does not depend on O
+// or on which lane met which candidate.  A candidate whose row lies outside the block reads nothing and takes key 0, below the key of -inf.
+#define MR_THREADS 256
+#define MR_WAVES (MR_THREADS / 64)
+#define MR_MAX_BLOCKS 2048
+
+template <bool F32>
+__global__ __launch_bounds__(MR_THREADS) void match_readout_kernel(int G, int O, const char* __restrict__ x, long ld, const int32_t* __restrict__ row,
+                                                                  long n_rows, int true_col, int false_col, const int32_t* __restrict__ gt,
+                                                                  float* __restrict__ score, int32_t* __restrict__ choice, int32_t* __restrict__ hit) {
+    constexpr int ES = F32 ? 4 : 2;
+    const int lane = threadIdx.x & 63;
+    for (long g = (long)blockIdx.x * MR_WAVES + (threadIdx.x >> 6); g < G; g += (long)gridDim.x * MR_WAVES) {   // uniform within a wave
+        aq_u64 best = 0;
+        for (int o = lane; o < O; o += 64) {
+            const long k = g * O + o;
+            const long r = row ? (long)row[k] : k;
+            float s = __uint_as_float(0x7fc00000u);
+            aq_u64 w = (uint32_t)(~(uint32_t)o);                 // key 0: the "NaN-last" class
+            if (r >= 0 && r < n_rows) {
+                const char* p = x + r * ld * ES;
+                const float t = aq_load<F32>(p, true_col), f = aq_load<F32>(p, false_col);
+                s = t / (t + f);
+                if (s != s) s = __uint_as_float(0x7fc00000u);   // one NaN pattern in `score`, whatever the division made
+                w = aq_word(s, o);
+            }
+            if (score) score[k] = s;
+            best = w > best ? w : best;
+        }
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            const aq_u64 ob = aq_shfl_xor(best, m);
+            best = ob > best ? ob : best;
+        }
+        if (lane == 0) {
+            const int c = (int)(~(uint32_t)best);
+            choice[g] = c;
+            if (hit) hit[g] = (c == gt[g]) ? 1 : 0;             // c lies in [0, O): a gt outside it never hits
+        }
+    }
+}
+
+extern "C" int lav_match_readout(void* stream, int G, int O, const void* logits, long ld, int dtype, const int32_t* row, long n_rows, int true_col,
+                                 int false_col, const int32_t* gt, float* score, int32_t* choice, int32_t* hit) {
+    LAV_REQUIRE(G >= 1 && O >= 1, "lav_match_readout: G=%d O=%d (both >= 1)", G, O);
+    LAV_REQUIRE(dtype == 0 || dtype == 1, "lav_match_readout: dtype=%d (0 bf16, 1 fp32)", dtype);
+    LAV_REQUIRE(ld >= 1 && true_col >= 0 && true_col < ld && false_col >= 0 && false_col < ld,
+                "lav_match_readout: columns %d / %d outside [0, ld = %ld)", true_col, false_col, ld);
+    LAV_REQUIRE(n_rows >= 0 && (row || n_rows >= (long)G * O), "lav_match_readout: %ld rows for %d x %d candidates and no row map", n_rows, G, O);
+    LAV_REQUIRE(logits && choice && (!hit || gt), "lav_match_readout: null pointer (logits, choice, or hit without gt)");
+    LAV_REQUIRE(((uintptr_t)logits % (dtype == 1 ? 4 : 2)) == 0, "lav_match_readout: logits are not aligned to their element size");
+    const long blocks = ((long)G + MR_WAVES - 1) / MR_WAVES;
+    const dim3 grid((unsigned)(blocks < MR_MAX_BLOCKS ? blocks : MR_MAX_BLOCKS));
+    if (dtype == 1)
+        hipLaunchKernelGGL(match_readout_kernel<true>, grid, dim3(MR_THREADS), 0, (hipStream_t)stream, G, O, (const char*)logits, ld, row, n_rows,
+                           true_col, false_col, gt, score, choice, hit);
+    else
+        hipLaunchKernelGGL(match_readout_kernel<false>, grid, dim3(MR_THREADS), 0, (hipStream_t)stream, G, O, (const char*)logits, ld, row, n_rows,
+                           true_col, false_col, gt, score, choice, hit);
+    return lav_check_launch("lav_match_readout");
+}

@@ -723,3 +723,108 @@ def synthetic_qa_loaders(args, tokzr, kind, n_steps, n_val, vocab, rank=0, world
     vl, _ = dl(SyntheticQA(args, n_val, "val", tokzr, kind, vocab), False)
     ts, _ = dl(SyntheticQA(args, n_val, "test", tokzr, kind, vocab), False)
     return tr, vl, ts, sampler
+
+
+# ---- synthetic captioning / retrieval / retrieval multiple choice (the other task types of main_multi_task_mlm.py) ----------------------------------
+class SyntheticCaption(torch.utils.data.Dataset):
+    """(img, txt, mask, img_key) items with the shapes Dataset_Caption emits (main_caption.py:17-46): [CLS] words [SEP] [PAD]..."""
+    prompt_text = "write a description about the video."
+
+    def __init__(self, args, n, split, tokzr):
+        self.a, self.n, self.split, self.tokzr = args, n, split, tokzr
+        self.yaml_file = f"_datasets/synthetic/{split}.yaml"
+        self.image_keys = [f"{split}{i}" for i in range(n)]
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed(i + (0 if self.split == "train" else 1 << 20))
+        X = self.a.size_txt + 1
+        img = torch.randn(self.a.size_frame, 3, self.a.size_img, self.a.size_img, generator=g)
+        k = int(torch.randint(4, X - 3, (1,), generator=g))
+        txt = torch.zeros(X, dtype=torch.long)
+        txt[0] = 101; txt[1:1 + k] = torch.randint(1000, 30000, (k,), generator=g); txt[1 + k] = 102
+        return img, txt, (txt != 0).long(), self.image_keys[i]
+
+    def get_prompt(self):
+        ids = torch.randint(1000, 30000, (7,), generator=torch.Generator().manual_seed(7))     # stands in for the tokenized prompt_text
+        return ids, torch.ones_like(ids)
+
+    @staticmethod
+    def collate_batch(inputs):
+        img, txt, mask, vid = map(list, zip(*inputs))
+        return {"img": torch.stack(img, 0), "txt": torch.stack(txt, 0), "mask": torch.stack(mask, 0), "img_keys": vid}
+
+
+class SyntheticRetrieval(torch.utils.data.Dataset):
+    """Random clips with captions laid out as Dataset_Retrieval_MLM.str2txt lays them out (main_retrieval_mlm.py:20-23): [CLS] words [SEP]
+    [PAD] * .. over size_txt tokens, then the appended [MASK], X = size_txt + 1; items (img, txt, mask, vid) with one video id per clip."""
+    prompt_text = "is the video-text paired, true or false?"
+
+    def __init__(self, args, n, split, tokzr, vocab=30522):
+        self.args, self.n, self.split, self.tokzr = args, int(n), split, tokzr
+        self.cls_id, self.sep_id, self.pad_id, self.mask_id = tokzr.convert_tokens_to_ids(
+            [tokzr.cls_token, tokzr.sep_token, tokzr.pad_token, tokzr.mask_token])
+        self.hi = min(30000, int(vocab))
+        self.base = {"train": 0, "val": 1 << 20, "test": 1 << 21}.get(split, 1 << 22)
+
+    def __len__(self):
+        return self.n
+
+    def get_prompt(self):
+        g = torch.Generator().manual_seed(11)
+        ids = torch.cat([torch.tensor([self.cls_id]), torch.randint(1000, self.hi, (8,), generator=g), torch.tensor([self.sep_id])])
+        return ids, torch.ones_like(ids)                   # stands in for the tokenized prompt_text
+
+    def str2txt(self, g):
+        S = int(self.args.size_txt)
+        k = int(torch.randint(2, max(3, S - 1), (1,), generator=g))
+        ids = [self.cls_id] + torch.randint(1000, self.hi, (min(k, S - 2),), generator=g).tolist() + [self.sep_id]
+        txt = torch.LongTensor(ids + [self.pad_id] * (S - len(ids)) + [self.mask_id])
+        mask = (txt != self.pad_id).long()
+        return txt, mask
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed(5 + 7 * i + self.base)
+        img = torch.randn(int(self.args.size_frame), 3, int(self.args.size_img), int(self.args.size_img), generator=g)
+        txt, mask = self.str2txt(g)
+        return img, txt, mask, self.base + i
+
+    def collate_batch(self, inputs):
+        img, txt, mask, vid = map(list, zip(*inputs))
+        return {"img": torch.stack(img, 0), "txt": torch.stack(txt, 0), "mask": torch.stack(mask, 0), "vid": vid}
+
+
+class SyntheticRetMC(SyntheticRetrieval):
+    """Random clips with size_option candidate texts each, laid out as Dataset_RetMC_MLM lays them out (main_retmc_mlm.py:16-52): every
+    candidate is a caption with the appended [MASK]; the [MASK] of the right candidate is labelled "true", the others "false"; items
+    (img, txt (O, X), mask (O, X), mask_ans (O, X))."""
+
+    def __init__(self, args, n, split, tokzr, vocab=30522):
+        super().__init__(args, n, split, tokzr, vocab)
+        self.size_option = int(getattr(args, "size_option", 5))
+        self.true_id, self.false_id = tokzr.convert_tokens_to_ids(["true", "false"])
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed(9 + 11 * i + self.base)
+        img = torch.randn(int(self.args.size_frame), 3, int(self.args.size_img), int(self.args.size_img), generator=g)
+        ans_idx = int(torch.randint(0, self.size_option, (1,), generator=g))
+        txt, mask, mask_ans = [], [], []
+        for o in range(self.size_option):
+            t, m = self.str2txt(g)
+            a = torch.ones_like(t) * -1
+            a[t == self.mask_id] = self.true_id if o == ans_idx else self.false_id
+            txt.append(t); mask.append(m); mask_ans.append(a)
+        return img, torch.stack(txt), torch.stack(mask), torch.stack(mask_ans)
+
+    def collate_batch(self, inputs):
+        img, txt, mask, mask_ans = map(list, zip(*inputs))
+        return {"img": torch.stack(img, 0), "txt": torch.stack(txt, 0), "mask": torch.stack(mask, 0), "mask_ans": torch.stack(mask_ans, 0)}
+
+
+def synthetic_loader(ds, args, train, rank=0, world=1):
+    """(DataLoader, sampler or None) over a synthetic dataset with its own collate_batch, batch size args.size_batch"""
+    sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=train) if world > 1 else None
+    return torch.utils.data.DataLoader(ds, batch_size=args.size_batch, sampler=sampler, shuffle=train and sampler is None,
+                                       num_workers=args.n_workers, pin_memory=True, drop_last=train, collate_fn=ds.collate_batch), sampler

@@ -886,3 +886,43 @@ def answer_readout(logits, V, labels, cand=(), splits=None, out=None):
                                      cand_np.ctypes.data_as(C.c_void_p) if cand_np.size else None, int(cand_np.size), splits, _p(ws), need,
                                      _p(out[0]), _p(out[1]), _p(out[2])), "lav_answer_readout")
     return out[0], out[1], out[2]
+
+
+def match_readout(logits, G, O, true_col, false_col, row=None, gt=None, want_score=False, out=None):
+    """(choice (G,) int32, hit (G,) int32 or None, score (G * O,) fp32 or None) on the device: lav_match_readout over G groups of O candidates of
+    a (n_rows, width) bf16 / fp32 logits view -- s = t / (t + f) of columns true_col / false_col of row[k] (row None: row k), choice = arg-max of
+    s over a group (NaN above every number, lowest o on a tie), hit = choice == gt.  row / gt: host arrays (checked here: a row outside
+    [0, n_rows) raises ValueError; then uploaded) or int32 device tensors (the caller vouches; the kernel reads nothing for a row outside the
+    block).  out: a (2, G) int32 device tensor for (choice, hit)."""
+    import numpy as np
+    if not (logits.dim() == 2 and logits.stride(-1) == 1 and logits.dtype in (bf16, torch.float32)):
+        raise ValueError("match_readout: logits must be a (rows, width) bf16 / fp32 view with unit column stride")
+    G, O = int(G), int(O)
+    n_rows, width = logits.shape
+    dev = logits.device
+    if not (0 <= int(true_col) < width and 0 <= int(false_col) < width):
+        raise ValueError(f"match_readout: columns {true_col} / {false_col} outside the {width} columns of the logits")
+
+    def dev_i32(a, n, what):
+        if a is None:
+            return None
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            if not (a.dtype == torch.int32 and a.is_contiguous() and a.numel() == n):
+                raise ValueError(f"match_readout: a device {what} must be a contiguous int32 tensor of {n} entries")
+            return a
+        a = np.ascontiguousarray(a.numpy() if isinstance(a, torch.Tensor) else a).reshape(-1)
+        if a.size != n:
+            raise ValueError(f"match_readout: {what} has {a.size} entries, expected {n}")
+        if what == "row" and a.size and (a.min() < 0 or a.max() >= n_rows):
+            raise ValueError(f"match_readout: row entry outside the {n_rows} rows of the logits")
+        return torch.from_numpy(a.astype(np.int32)).to(dev, non_blocking=True)
+
+    row_d, gt_d = dev_i32(row, max(G, 0) * max(O, 0), "row"), dev_i32(gt, max(G, 0), "gt")
+    if out is None:
+        out = torch.empty((2, max(G, 1)), dtype=torch.int32, device=dev)       # a G < 1 is the entry's to reject
+    elif not (out.dtype == torch.int32 and out.shape == (2, G) and out.is_contiguous()):
+        raise ValueError(f"match_readout: out must be a contiguous (2, {G}) int32 tensor")
+    score = torch.empty(max(G, 0) * max(O, 0), dtype=torch.float32, device=dev) if want_score else None
+    L.check(L.lib.lav_match_readout(_s(), G, O, _p(logits), _ld(logits), int(logits.dtype == torch.float32), _p(row_d), n_rows, int(true_col),
+                                    int(false_col), _p(gt_d), _p(score), _p(out[0]), _p(out[1]) if gt_d is not None else None), "lav_match_readout")
+    return out[0], (out[1] if gt_d is not None else None), score

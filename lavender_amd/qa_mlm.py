@@ -56,19 +56,12 @@ def host_labels_of(args, batch, out):
     return out
 
 
-class LAVENDER_QAOE_MLM(LAVENDER_Base):
-    def __init__(self, args, tokzr=None):
-        super().__init__(args, tokzr)
-        assert getattr(args, "size_vocab", -1) == -1, "the MLM-head QA model answers with the tokenizer's vocabulary (size_vocab = -1)"
-        cfg = BertConfigLite.from_pretrained(args.tokenizer)
-        self.fc_mtm = BertOnlyMLMHead(cfg)
-        sd = load_hf_state(args.tokenizer, [("cls.", "")])
-        if sd:
-            load_hf_into(self.fc_mtm, sd, "MLM head (HF checkpoint)")
-        self.task_tok2id = {"vtm": 0, "mc": 1, "oe": 2, "cap": 3}
-        self.emb_task = nn.Parameter(0.02 * torch.randn(10, self.hidden_size))
+class QAForwardMixin:
+    """What the MLM-head QA callers share (a LAVENDER_Base with the MLM head `fc_mtm`): the forwards of LAVENDER_QAOE_MLM / LAVENDER_QAMC_MLM
+    (qa_forward) and LAVENDER_RetMC_MLM (retmc_forward), the -1 labels of the pre-text and the rows path (qa_forward_rows, answer_rows).
+    multi_task.LAVENDER_Multi_Task inherits the same methods."""
 
-    def forward(self, batch):
+    def qa_forward(self, batch):
         """main_qaoe_mlm_lsmdc_fib.py:79-93 / main_qamc_mlm.py:124-140: (B, X, vocab) logits over the text positions and the
         (B, X) labels (-1 everywhere but the [MASK])."""
         feat_img, mask_img, feat_txt, mask_txt, ans, Lv, _ = self._front(batch)
@@ -91,14 +84,14 @@ class LAVENDER_QAOE_MLM(LAVENDER_Base):
         return feat_img, mask_img, feat_txt, mask_txt, ans, (1 + _h * _w) * _T, feat_txt.shape[1] - txt.shape[1]
 
     # ---- rows path: only the labelled rows ------------------------------------------------------------------------------------
-    def forward_rows(self, batch):
-        """forward restricted to the labelled positions: ((n_lab, vocab) logits, (n_lab,) labels) in the order of `ans[ans != -1]`.  The batch
+    def qa_forward_rows(self, batch, full=None):
+        """qa_forward (or the caller's own `full` forward) restricted to the labelled positions: ((n_lab, vocab) logits, (n_lab,) labels) in the order of `ans[ans != -1]`.  The batch
         carries the host copy of its labels as batch["_lab_host"] (qa_mlm.host_labels_of); the encoder runs as in forward, engine.RowGatherFn takes
         the labelled rows of the last hidden state and fc_mtm runs on those.  Any number of labelled rows per sample; a batch without a host
         copy or without any label takes forward() (flattened), so the loss behaves as on the full path."""
         host = batch.get("_lab_host")
         if host is None or not bool((host != -1).any()):
-            out, ans = self.forward({k: v for k, v in batch.items() if k != "_lab_host"})
+            out, ans = (full or self.qa_forward)({k: v for k, v in batch.items() if k != "_lab_host"})
             return out.flatten(0, 1), ans.flatten()
         feat_img, mask_img, feat_txt, mask_txt, _, Lv, Lp = self._front(batch)
         lr = label_rows(host, Lp)
@@ -153,15 +146,9 @@ class LAVENDER_QAOE_MLM(LAVENDER_Base):
         logits = self.fc_mtm(y)
         return K.answer_readout(logits, logits.shape[-1], lr.label, cand if cand is not None else ())
 
-
-class LAVENDER_QAMC_MLM(LAVENDER_QAOE_MLM):
-    """main_qamc_mlm.py:109-140: the multiple-choice model is the same graph (its task-specific `fc` is deleted in favour of the
-    MLM head); only the text it is fed and the agent's evaluation differ."""
-
-
-class LAVENDER_RetMC_MLM(LAVENDER_QAOE_MLM):
-    def forward(self, batch):
-        """main_retmc_mlm.py:89-113: txt / mask / mask_ans are (B, O, X); logits (B * O, X, vocab), labels back as (B, O, X)."""
+    def retmc_forward(self, batch, rows=False):
+        """main_retmc_mlm.py:89-113: txt / mask / mask_ans are (B, O, X); logits (B * O, X, vocab), labels back as (B, O, X).  rows: the MLM head on the
+        labelled positions only, by the host copy batch["_lab_host"] (B, O, X) of the labels -- ((n_lab, vocab) logits, (n_lab,) labels)."""
         img, txt, mask, ans = [batch.get(key) for key in ["img", "txt", "mask", "mask_ans"]]
         (_B, _T, _, _H, _W), (_, _O, _X) = img.shape, txt.shape
         _h, _w = _H // 32, _W // 32
@@ -171,8 +158,43 @@ class LAVENDER_RetMC_MLM(LAVENDER_QAOE_MLM):
         ans, mask_txt, feat_txt = self.prepro_txt_inputs(ans, mask_txt, feat_txt, task_name=task_name, prompt=prompt)
         vi, ti = np.repeat(np.arange(_B), _O), np.arange(_B * _O)       # video i with each of its O texts (expand + flatten, :100-103)
         out, _ = self.go_cross_pairs(feat_img, mask_img, feat_txt, mask_txt, vi, ti)
+        if rows:
+            Lv, Lp = (1 + _h * _w) * _T, feat_txt.shape[1] - _X
+            lr = label_rows(batch["_lab_host"].flatten(0, 1), Lp)
+            n, L, Hd = out.shape
+            got = E.RowGatherFn.apply(out.reshape(n * L, Hd), lr.sample * L + Lv + Lp + lr.pos)
+            return self.fc_mtm(got), torch.from_numpy(lr.label.astype(np.int64)).to(got.device, non_blocking=True)
         out = self.fc_mtm(out[:, (1 + _h * _w) * _T:])
         return out, ans.view(_B, _O, -1)
+
+
+class LAVENDER_QAOE_MLM(QAForwardMixin, LAVENDER_Base):
+    def __init__(self, args, tokzr=None):
+        super().__init__(args, tokzr)
+        assert getattr(args, "size_vocab", -1) == -1, "the MLM-head QA model answers with the tokenizer's vocabulary (size_vocab = -1)"
+        cfg = BertConfigLite.from_pretrained(args.tokenizer)
+        self.fc_mtm = BertOnlyMLMHead(cfg)
+        sd = load_hf_state(args.tokenizer, [("cls.", "")])
+        if sd:
+            load_hf_into(self.fc_mtm, sd, "MLM head (HF checkpoint)")
+        self.task_tok2id = {"vtm": 0, "mc": 1, "oe": 2, "cap": 3}
+        self.emb_task = nn.Parameter(0.02 * torch.randn(10, self.hidden_size))
+
+    def forward(self, batch):
+        return self.qa_forward(batch)
+
+    def forward_rows(self, batch):
+        return self.qa_forward_rows(batch, self.forward)
+
+
+class LAVENDER_QAMC_MLM(LAVENDER_QAOE_MLM):
+    """main_qamc_mlm.py:109-140: the multiple-choice model is the same graph (its task-specific `fc` is deleted in favour of the
+    MLM head); only the text it is fed and the agent's evaluation differ."""
+
+
+class LAVENDER_RetMC_MLM(LAVENDER_QAOE_MLM):
+    def forward(self, batch):
+        return self.retmc_forward(batch)
 
 
 class Agent_RetMC_MLM(Agent_Base):

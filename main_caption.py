@@ -17,6 +17,7 @@ import torch
 
 import lavender_amd as LA
 from lavender_amd.args import get_args
+from lavender_amd.data import SyntheticCaption  # noqa: F401  (lived here before the multi-task entry point shared it)
 from lavender_amd.dist import get_rank, get_world_size, is_main_process
 
 
@@ -26,37 +27,6 @@ class _Tok:
 
     def convert_tokens_to_ids(self, toks):
         return [self.ids[t] for t in toks]
-
-
-class SyntheticCaption(torch.utils.data.Dataset):
-    """(img, txt, mask, img_key) items with the shapes Dataset_Caption emits (main_caption.py:17-46): [CLS] words [SEP] [PAD]..."""
-    prompt_text = "write a description about the video."
-
-    def __init__(self, args, n, split, tokzr):
-        self.a, self.n, self.split, self.tokzr = args, n, split, tokzr
-        self.yaml_file = f"_datasets/synthetic/{split}.yaml"
-        self.image_keys = [f"{split}{i}" for i in range(n)]
-
-    def __len__(self):
-        return self.n
-
-    def __getitem__(self, i):
-        g = torch.Generator().manual_seed(i + (0 if self.split == "train" else 1 << 20))
-        X = self.a.size_txt + 1
-        img = torch.randn(self.a.size_frame, 3, self.a.size_img, self.a.size_img, generator=g)
-        k = int(torch.randint(4, X - 3, (1,), generator=g))
-        txt = torch.zeros(X, dtype=torch.long)
-        txt[0] = 101; txt[1:1 + k] = torch.randint(1000, 30000, (k,), generator=g); txt[1 + k] = 102
-        return img, txt, (txt != 0).long(), self.image_keys[i]
-
-    def get_prompt(self):
-        ids = torch.randint(1000, 30000, (7,), generator=torch.Generator().manual_seed(7))     # stands in for the tokenized prompt_text
-        return ids, torch.ones_like(ids)
-
-    @staticmethod
-    def collate_batch(inputs):
-        img, txt, mask, vid = map(list, zip(*inputs))
-        return {"img": torch.stack(img, 0), "txt": torch.stack(txt, 0), "mask": torch.stack(mask, 0), "img_keys": vid}
 
 
 def loader(ds, args, train):
